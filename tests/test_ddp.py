@@ -76,6 +76,9 @@ def _ragged_worker(rank, world, port, tmpdir):
     os.environ["RANK"] = str(rank)
     os.environ["LOCAL_RANK"] = str(rank)
     os.environ["WORLD_SIZE"] = str(world)
+    # this is the CPU test: join over gloo even where a GPU is present
+    # (train() keeps an already initialised process group)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         from nats_amd.engine.trainer import train
 
@@ -128,6 +131,8 @@ def test_bench_multirank_torchrun_contract(tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ)
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
+    # CPU ranks even on a GPU machine (RCCL refuses 2 ranks on one GPU)
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

@@ -190,6 +190,49 @@ def test_bench_contract(tmp_path):
     assert r["config"]["global_batch"] == r["config"]["batch_per_gpu"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32
+    .npy files, identical from run to run (seeded inputs and weights);
+    --full is accepted and leaves the result line's keys in place."""
+    import json
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--config", "toy",
+             "--dump-outputs", str(d)] + extra,
+            capture_output=True, text=True, timeout=300, cwd=repo)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = [l for l in out.stdout.splitlines()
+                 if l.strip().startswith("{")]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        arrs = {f: numpy.load(str(d / f)) for f in sorted(os.listdir(d))}
+        assert sorted(arrs) == ["cost.npy"]
+        for f, a in arrs.items():
+            assert a.dtype == numpy.float32 and numpy.isfinite(a).all(), f
+        assert arrs["cost.npy"].shape == (1,)
+        assert arrs["cost.npy"][0] == numpy.float32(
+            r["config"]["final_cost"])
+        dumps.append(arrs)
+    for f in dumps[0]:
+        if r["dtype"] == "fp32":
+            # CPU: same inputs, same arithmetic, same bits
+            numpy.testing.assert_array_equal(dumps[0][f], dumps[1][f],
+                                             err_msg=f)
+        else:
+            # GPU: atomically accumulated fp32 sums may round differently
+            # into bf16 (eps 2^-8) from run to run; allow one such step
+            numpy.testing.assert_allclose(dumps[0][f], dumps[1][f],
+                                          rtol=2.0 ** -8, err_msg=f)
+
+
 def test_nan_failure_detection(toy_corpus, tmp_path):
     """NaN/Inf training cost -> hard abort returning the
     (1., 1., 1.) sentinel (nats.py:1415-1417); NaN validation cost ->

@@ -1,20 +1,25 @@
-"""Live parity: our ROUGE port vs the reference's ROUGE.pl run by perl
-(skipped when perl or the reference checkout is unavailable)."""
+"""Parity: our ROUGE port vs the reference's ROUGE.pl.
 
+The perl script's printed averages for the inputs below are stored, with
+the inputs themselves, in tests/golden/rouge_perl_parity.json, so the
+check needs neither perl nor a checkout of the reference."""
+
+import json
 import os
-import shutil
-import subprocess
 
 import numpy
 import pytest
 
 from nats_amd.decode.rouge import format_report
 
-ROUGE_PL = "/root/reference/scripts/ROUGE.pl"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                      "rouge_perl_parity.json")
 
-pytestmark = pytest.mark.skipif(
-    shutil.which("perl") is None or not os.path.exists(ROUGE_PL),
-    reason="perl or reference ROUGE.pl unavailable")
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(GOLDEN) as f:
+        return {c["seed"]: c for c in json.load(f)["cases"]}
 
 
 def _mk_files(tmp_path, seed=0, n=25):
@@ -34,13 +39,17 @@ def _mk_files(tmp_path, seed=0, n=25):
 @pytest.mark.parametrize("seed", [0, 1, 2])
 @pytest.mark.parametrize("nsize,metric", [(1, "N"), (2, "N"), (3, "N"),
                                           (1, "L")])
-def test_matches_perl(tmp_path, seed, nsize, metric):
+def test_matches_perl(tmp_path, golden, seed, nsize, metric):
     ref, sys_ = _mk_files(tmp_path, seed)
-    perl_out = subprocess.run(
-        ["perl", ROUGE_PL, str(nsize), metric, ref, sys_],
-        capture_output=True, text=True, check=True).stdout
+    case = golden[seed]
+    # the stored perl output belongs to exactly these inputs
+    with open(ref) as f:
+        assert f.read() == case["ref"]
+    with open(sys_) as f:
+        assert f.read() == case["sys"]
     ours = format_report(ref, sys_, nsize, metric)
     # compare the three printed averages
-    perl_nums = perl_out.strip().splitlines()[-1].split()
+    perl_nums = case["perl_last_line"]["%d-%s" % (nsize, metric)].split()
     our_nums = ours.strip().splitlines()[-1].split()
-    assert perl_nums == our_nums, (perl_out, ours)
+    assert len(perl_nums) == 3
+    assert perl_nums == our_nums, (perl_nums, ours)

@@ -95,7 +95,7 @@ def test_decode_matches_offline_driver(tiny_server):
     out = os.path.join(d, "serve_out.txt")
     generate_file(os.path.join(d, "model.npz"), os.path.join(d, "toy_train_input.txt.pkl"),
                   src, out, k=svc.k, normalize=True, n_process=1,
-                  verbose=False, maxlen=svc.maxlen)
+                  verbose=False, maxlen=svc.maxlen, devices=["cpu"])
     with open(out) as f:
         offline = [ln.strip() for ln in f.read().splitlines()]
     served = svc.summarize_many(lines)

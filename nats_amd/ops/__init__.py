@@ -107,7 +107,7 @@ def gru_scan_bidir(xg0, xc0, mask0, U0, Ux0, xg1, xc1, mask1, U1, Ux1):
         # chunk jobs concurrent in one launch — same barrier count as 32)
         direct_max = MAX_KERNEL_BATCH
         if _hip_ext() is not None and _hip_ext().gru_persistent_ok(
-                U0.shape[0]):
+                U0.shape[0], 2 * MAX_KERNEL_BATCH):
             direct_max = 2 * MAX_KERNEL_BATCH
         if B <= direct_max:
             return gru_scan_bidir_hip(xg0, xc0, mask0, U0, Ux0, xg1, xc1,

@@ -57,6 +57,61 @@ __device__ __forceinline__ void store_cd_rowmajor(float* base, const f32x4& d,
   for (int i = 0; i < 4; ++i) base[(long)(rbase + i) * ld + col] = d[i];
 }
 
+constexpr int JB = 16;  // output columns per workgroup (one MFMA N-tile)
+
+static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Scatter a C/D fragment into one [32][JB+1] LDS tile (rows row0..row0+15):
+// the MFMA -> pointwise exchange after every gate/recurrent K-loop.
+__device__ __forceinline__ void store_cd_lds(float (*dst)[JB + 1],
+                                             const f32x4& acc, int row0) {
+  const int lane = threadIdx.x & (NATS_WAVE - 1);
+  const int col = lane & 15;
+  const int rbase = row0 + (lane >> 4) * 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dst[rbase + i][col] = acc[i];
+}
+
+// Block reductions: wave shuffle-down, one LDS slot per wave, thread 0
+// combines the slots in wave order and broadcasts through a separate word.
+// The scratch holds the largest legal block (1024 threads = 16 waves)
+// whatever the launch width, and the trailing barrier keeps a following
+// call from overwriting it while the result is still being read.
+constexpr int NATS_MAX_WAVES = 1024 / NATS_WAVE;
+
+// one scratch per kernel, shared by every reduction in it
+__device__ __forceinline__ float* block_reduce_scratch() {
+  __shared__ float red[NATS_MAX_WAVES + 1];  // per-wave slots | broadcast
+  return red;
+}
+
+template <bool MAX>
+__device__ __forceinline__ float block_reduce(float v) {
+  auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : a + b; };
+  float* red = block_reduce_scratch();
+#pragma unroll
+  for (int off = NATS_WAVE / 2; off > 0; off >>= 1)
+    v = op(v, __shfl_down(v, off));
+  if ((threadIdx.x & (NATS_WAVE - 1)) == 0) red[threadIdx.x / NATS_WAVE] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float r = MAX ? -INFINITY : 0.f;
+    for (int w = 0; w < (int)blockDim.x / NATS_WAVE; ++w) r = op(r, red[w]);
+    red[NATS_MAX_WAVES] = r;
+  }
+  __syncthreads();
+  const float r = red[NATS_MAX_WAVES];
+  __syncthreads();
+  return r;
+}
+
+__device__ __forceinline__ float block_reduce_sum(float v) {
+  return block_reduce<false>(v);
+}
+__device__ __forceinline__ float block_reduce_max(float v) {
+  return block_reduce<true>(v);
+}
+
 // 4-deep software-pipelined MFMA K-loop: four iterations' fragment loads
 // (both operands) stay in flight ahead of each MFMA so the L2 latency of
 // the 16 scattered 16B lines per fragment amortises over 4 iterations.

@@ -47,8 +47,6 @@
 
 namespace {
 
-constexpr int JB = 16;
-
 // ---------------- small GEMM: pstate = h1 @ W_att ----------------
 // A = [32][ldK] bf16 (zero-padded), Bt = [Npad][ldK] bf16. Split-K over
 // grid.z into Cpart [KS][32][N] f32 partials (the unsplit version was 14
@@ -154,8 +152,6 @@ __global__ __launch_bounds__(1024) void cond_attn_softmax(
     }
   }
   const int b = blockIdx.x;
-  __shared__ float red[256 / NATS_WAVE];
-  __shared__ float bcast;
 
   // masked positions must not influence the max: they are zeroed AFTER
   // exp, but a padded row's e shifting M changes rounding for the real
@@ -166,22 +162,10 @@ __global__ __launch_bounds__(1024) void cond_attn_softmax(
     if (ctx_mask != nullptr && ctx_mask[(long)s * B + b] == 0.f) continue;
     lmax = fmaxf(lmax, e_buf[(long)s * B + b]);
   }
-#pragma unroll
-  for (int off = NATS_WAVE / 2; off > 0; off >>= 1)
-    lmax = fmaxf(lmax, __shfl_down(lmax, off));
-  if ((threadIdx.x & (NATS_WAVE - 1)) == 0)
-    red[threadIdx.x / NATS_WAVE] = lmax;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = red[0];
-    for (int w = 1; w < (int)blockDim.x / NATS_WAVE; ++w)
-      M = fmaxf(M, red[w]);
-    bcast = M;
-  }
-  __syncthreads();
+  const float bmax = block_reduce_max(lmax);
   // all-masked rows cannot occur (every sequence has >= 1 real token),
   // but guard the degenerate -inf max anyway
-  const float M = isfinite(bcast) ? bcast : 0.f;
+  const float M = isfinite(bmax) ? bmax : 0.f;
 
   float lsum = 0.f;
   for (int s = threadIdx.x; s < Ts; s += blockDim.x) {
@@ -191,19 +175,7 @@ __global__ __launch_bounds__(1024) void cond_attn_softmax(
     alphas_t[(long)b * Ts + s] = a;  // unnormalised, fixed below
     lsum += a;
   }
-#pragma unroll
-  for (int off = NATS_WAVE / 2; off > 0; off >>= 1)
-    lsum += __shfl_down(lsum, off);
-  if ((threadIdx.x & (NATS_WAVE - 1)) == 0)
-    red[threadIdx.x / NATS_WAVE] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float S = 0.f;
-    for (int w = 0; w < (int)blockDim.x / NATS_WAVE; ++w) S += red[w];
-    bcast = S;
-  }
-  __syncthreads();
-  const float inv = 1.f / bcast;
+  const float inv = 1.f / block_reduce_sum(lsum);
 
   const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
   for (int s = threadIdx.x; s < Ts; s += blockDim.x) {
@@ -305,13 +277,7 @@ __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const bf16_t* brow = W1pk + (long)(wg * 4 + g) * JB * K1;
   NATS_MFMA_KLOOP(acc, hc_bf, 16 * m, K1, brow, 0, K1, kbeg, kend);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pre[g][ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(pre[g][ks], acc, 16 * m);
   __syncthreads();
 
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
@@ -319,25 +285,18 @@ __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
     const int c = idx % JB;
     const int j = j0 + c;
     if (j >= H) continue;
-    const float r2 =
-        nats_sigmoid(pre[0][0][b][c] + pre[0][1][b][c] + b1[j]);
-    const float u2 =
-        nats_sigmoid(pre[1][0][b][c] + pre[1][1][b][c] + b1[H + j]);
     const float pxa = pre[2][0][b][c] + pre[2][1][b][c];
     const float pxb = pre[3][0][b][c] + pre[3][1][b][c];
-    const float hbar = tanhf((pxa + bx1[j]) * r2 + pxb);
-    const float h1v = h1_t[(long)b * H + j];
-    float h2 = u2 * h1v + (1.f - u2) * hbar;
-    if (mask_t != nullptr) {
-      const float mm = mask_t[b];
-      h2 = mm * h2 + (1.f - mm) * h1v;
-    }
-    h2_t[(long)b * H + j] = h2;
-    h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)h2;
-    saved1_t[(long)b * 4 * H + j] = (bf16_t)r2;
-    saved1_t[(long)b * 4 * H + H + j] = (bf16_t)u2;
+    const GruCellFwd o = gru_cell_fwd(
+        pre[0][0][b][c] + pre[0][1][b][c] + b1[j],
+        pre[1][0][b][c] + pre[1][1][b][c] + b1[H + j], pxa + bx1[j], pxb,
+        h1_t[(long)b * H + j], mask_t, b);
+    h2_t[(long)b * H + j] = o.hnew;
+    h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
+    saved1_t[(long)b * 4 * H + j] = (bf16_t)o.r;
+    saved1_t[(long)b * 4 * H + H + j] = (bf16_t)o.u;
     saved1_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)pxa;
-    saved1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)hbar;
+    saved1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.hbar;
   }
 }
 
@@ -372,13 +331,7 @@ __global__ __launch_bounds__(1024) void cond_gru1_gemm_splitk(
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const bf16_t* brow = W1pk + (long)(wg * 4 + g) * JB * K1;
   NATS_MFMA_KLOOP(acc, hc_bf, 16 * m, K1, brow, 0, K1, kbeg, kend);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pre[g][ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(pre[g][ks], acc, 16 * m);
   __syncthreads();
 
   float* dst = part + ((long)ksb * 4 + 0) * 32 * Hpad;
@@ -417,22 +370,15 @@ __global__ void cond_gru1_step_pointwise(
       p2 += pk[(long)2 * 32 * Hpad + bj];
       p3 += pk[(long)3 * 32 * Hpad + bj];
     }
-    const float r2 = nats_sigmoid(p0 + b1[j]);
-    const float u2 = nats_sigmoid(p1 + b1[H + j]);
     const float pxa = p2;
-    const float hbar = tanhf((pxa + bx1[j]) * r2 + p3);
-    const float h1v = h1_t[idx];
-    float h2 = u2 * h1v + (1.f - u2) * hbar;
-    if (mask_t != nullptr) {
-      const float mm = mask_t[b];
-      h2 = mm * h2 + (1.f - mm) * h1v;
-    }
-    h2_t[idx] = h2;
-    h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)h2;
-    saved1_t[(long)b * 4 * H + j] = (bf16_t)r2;
-    saved1_t[(long)b * 4 * H + H + j] = (bf16_t)u2;
+    const GruCellFwd o = gru_cell_fwd(p0 + b1[j], p1 + b1[H + j],
+                                      pxa + bx1[j], p3, h1_t[idx], mask_t, b);
+    h2_t[idx] = o.hnew;
+    h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
+    saved1_t[(long)b * 4 * H + j] = (bf16_t)o.r;
+    saved1_t[(long)b * 4 * H + H + j] = (bf16_t)o.u;
     saved1_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)pxa;
-    saved1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)hbar;
+    saved1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.hbar;
   }
 }
 
@@ -491,24 +437,19 @@ __global__ void cond_gru1_bwd_pointwise(
     const float hbar = (float)saved1_t[(long)b * 4 * H + 3 * H + j];
     const float h1v = h1_all_t[idx];
     const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-    const float du2 = dh2 * mm * (h1v - hbar);
-    const float dhbar = dh2 * mm * (1.f - u2);
-    const float dpx2 = dhbar * (1.f - hbar * hbar);
-    const float dpxa_lin = dpx2 * r2;
-    const float dr2 = dpx2 * (pxa + bx1[j]);
-    const float dpr2 = dr2 * r2 * (1.f - r2);
-    const float dpu2 = du2 * u2 * (1.f - u2);
-    ddirect_h1[idx] = dh2 * (mm * u2 + (1.f - mm));
-    dstep1[(long)b * ldK3 + j] = (bf16_t)dpr2;
-    dstep1[(long)b * ldK3 + H + j] = (bf16_t)dpu2;
-    dstep1[(long)b * ldK3 + 2 * H + j] = (bf16_t)dpxa_lin;
-    dstepC[(long)b * ldK3 + j] = (bf16_t)dpr2;
-    dstepC[(long)b * ldK3 + H + j] = (bf16_t)dpu2;
-    dstepC[(long)b * ldK3 + 2 * H + j] = (bf16_t)dpx2;
-    dpre1_t[(long)b * 4 * H + j] = (bf16_t)dpr2;
-    dpre1_t[(long)b * 4 * H + H + j] = (bf16_t)dpu2;
-    dpre1_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)dpx2;
-    dpre1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)dpxa_lin;
+    const GruCellBwd o =
+        gru_cell_bwd(dh2, r2, u2, pxa + bx1[j], hbar, h1v, mm);
+    ddirect_h1[idx] = o.ddirect;
+    dstep1[(long)b * ldK3 + j] = (bf16_t)o.dpr;
+    dstep1[(long)b * ldK3 + H + j] = (bf16_t)o.dpu;
+    dstep1[(long)b * ldK3 + 2 * H + j] = (bf16_t)o.dpxl;
+    dstepC[(long)b * ldK3 + j] = (bf16_t)o.dpr;
+    dstepC[(long)b * ldK3 + H + j] = (bf16_t)o.dpu;
+    dstepC[(long)b * ldK3 + 2 * H + j] = (bf16_t)o.dpx;
+    dpre1_t[(long)b * 4 * H + j] = (bf16_t)o.dpr;
+    dpre1_t[(long)b * 4 * H + H + j] = (bf16_t)o.dpu;
+    dpre1_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)o.dpx;
+    dpre1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.dpxl;
   }
 }
 
@@ -559,13 +500,7 @@ __global__ __launch_bounds__(384) void cond_bwd_gemm_dual_gate(
   const int kend = min(Kpad, (ks + 1) * kchunk);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   NATS_MFMA_KLOOP(acc, dstep, 16 * m, Kpad, Wt, i0, Kpad, kbeg, kend);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(part[ks], acc, 16 * m);
   __syncthreads();
 
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
@@ -643,13 +578,7 @@ __global__ __launch_bounds__(384) void cond_dh_carry_gemm_split(
   const int kend = min(hend, kbeg + kchunk);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   NATS_MFMA_KLOOP(acc, dstep, 16 * m, Kpad, Wt, i0, Kpad, kbeg, kend);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(part[ks], acc, 16 * m);
   __syncthreads();
   float* o = out + (long)ks2 * B * H;
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
@@ -683,13 +612,7 @@ __global__ __launch_bounds__(384) void cond_dh1_att_gemm(
     bf16x8 bfr = frag_bt_rowmajor(WattB, i0, Apad, k);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, acc, 0, 0, 0);
   }
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(part[ks], acc, 16 * m);
   __syncthreads();
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
     const int b = idx / JB;
@@ -756,21 +679,11 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_dot(
     const float* __restrict__ alphas_t, const float* __restrict__ dal_buf,
     float* __restrict__ dot_buf, int B, int Ts) {
   const int b = blockIdx.x;
-  __shared__ float red[256 / NATS_WAVE];
   float part = 0.f;
   for (int s = threadIdx.x; s < Ts; s += blockDim.x)
     part += alphas_t[(long)b * Ts + s] * dal_buf[(long)s * B + b];
-#pragma unroll
-  for (int off = NATS_WAVE / 2; off > 0; off >>= 1)
-    part += __shfl_down(part, off);
-  if ((threadIdx.x & (NATS_WAVE - 1)) == 0)
-    red[threadIdx.x / NATS_WAVE] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float S = 0.f;
-    for (int w = 0; w < (int)blockDim.x / NATS_WAVE; ++w) S += red[w];
-    dot_buf[b] = S;
-  }
+  const float S = block_reduce_sum(part);
+  if (threadIdx.x == 0) dot_buf[b] = S;
 }
 
 // attention backward, stage 2 (grid (B, ceil(Ts/256))): softmax backward,
@@ -866,7 +779,6 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
   const int chunk = (Ts + SCH - 1) / SCH;
   float* sm_de = (float*)smem_raw;      // [chunk]
   float* sm_au = sm_de + chunk;         // [chunk]
-  __shared__ float red[256 / NATS_WAVE];
   const int b = blockIdx.x;
   const int sbeg = blockIdx.y * chunk;
   const int send = min(Ts, sbeg + chunk);
@@ -879,15 +791,8 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
     sm_au[s - sbeg] = accA_used_t[(long)b * Ts + s];
     dc += de;
   }
-#pragma unroll
-  for (int off = NATS_WAVE / 2; off > 0; off >>= 1) dc += __shfl_down(dc, off);
-  if ((threadIdx.x & (NATS_WAVE - 1)) == 0) red[threadIdx.x / NATS_WAVE] = dc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float S = 0.f;
-    for (int w = 0; w < (int)blockDim.x / NATS_WAVE; ++w) S += red[w];
-    atomicAdd(gdcatt, S);
-  }
+  const float dc_blk = block_reduce_sum(dc);  // also orders sm_de / sm_au
+  if (threadIdx.x == 0) atomicAdd(gdcatt, dc_blk);
   for (int i = threadIdx.x; i < A; i += blockDim.x) {
     const bf16_t* prow = pc_buf + ((long)b * A + i) * Tpad8;
     const float ua = Uatt[i];
@@ -929,8 +834,6 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
   }
 }
 
-inline int cdiv_i(int a, int b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 // ================= host: forward =================
@@ -953,7 +856,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
   TORCH_CHECK(pctx.dtype() == torch::kFloat32 && pctx.is_contiguous());
   const int Hpad = Upk2.size(1);
   const int K1 = W1pk.size(1);
-  const int ngrpH = cdiv_i(H, JB);
+  const int ngrpH = cdiv(H, JB);
   TORCH_CHECK(Upk2.size(0) == ngrpH * 3 * JB);
   TORCH_CHECK(W1pk.size(0) == ngrpH * 4 * JB);
 
@@ -987,21 +890,12 @@ std::vector<torch::Tensor> cond_gru_fwd(
   auto init_f = init_state.contiguous().to(torch::kFloat32);
   h2bf[0].slice(0, 0, B).slice(1, 0, H).copy_(init_f.to(torch::kBFloat16));
 
-  const float* mask_p = nullptr;
-  torch::Tensor mask_c;
-  if (mask.has_value()) {
-    mask_c = mask->contiguous().to(torch::kFloat32);
-    mask_p = mask_c.data_ptr<float>();
-  }
-  const float* cmask_p = nullptr;
-  torch::Tensor cmask_c;
-  if (ctx_mask.has_value()) {
-    cmask_c = ctx_mask->contiguous().to(torch::kFloat32);
-    cmask_p = cmask_c.data_ptr<float>();
-  }
+  const OptF32 mask_f(mask), cmask_f(ctx_mask);
+  const float* mask_p = mask_f.p;
+  const float* cmask_p = cmask_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  const int Apad16 = cdiv_i(A, 16) * 16;
+  const int Apad16 = cdiv(A, 16) * 16;
   const long hbstride = (long)32 * Hpad;
   bf16_t* h2bf_p = (bf16_t*)h2bf.data_ptr();
 
@@ -1016,7 +910,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
                          dim3(384), 0, stream, h2bf_p + (t % 2) * hbstride,
                          (const bf16_t*)Upk2.data_ptr(),
                          gru2_part.data_ptr<float>(), Hpad);
-      hipLaunchKernelGGL(nats_gru2_step_pointwise, dim3(cdiv_i(B * H, 256)),
+      hipLaunchKernelGGL(nats_gru2_step_pointwise, dim3(cdiv(B * H, 256)),
                          dim3(256), 0, stream, gru2_part.data_ptr<float>(),
                          GRU2_KS, h2prev,
                          (const bf16_t*)yg.data_ptr() + (long)t * B * 2 * H,
@@ -1044,7 +938,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
                        (int)WattPk.size(1));
     // 3) attention scores (s- and A-parallel) + softmax + acc_alpha
     hipLaunchKernelGGL(cond_attn_escore,
-                       dim3(B, cdiv_i(Ts, 256), A >= 16 ? 4 : 1), dim3(256),
+                       dim3(B, cdiv(Ts, 256), A >= 16 ? 4 : 1), dim3(256),
                        3 * A * sizeof(float), stream, pctx.data_ptr<float>(),
                        ps_part.data_ptr<float>(), PS_KS,
                        accA.data_ptr<float>(), Dwei.data_ptr<float>(),
@@ -1063,11 +957,11 @@ std::vector<torch::Tensor> cond_gru_fwd(
     // 4) weighted context (s-chunked partials) + gate + acc_ctx
     // (ctxpre_f32 arrives zeroed: gate_fwd re-zeroes it after reading)
     hipLaunchKernelGGL(cond_attn_ctx_partial,
-                       dim3(B, cdiv_i(C, 256), SCH), dim3(256), 0, stream,
+                       dim3(B, cdiv(C, 256), SCH), dim3(256), 0, stream,
                        (const bf16_t*)ctx_bf.data_ptr(),
                        alphas_all.data_ptr<float>() + (long)t * B * Ts,
                        ctxpre_f32.data_ptr<float>(), B, Ts, C, SCH);
-    hipLaunchKernelGGL(cond_attn_gate_fwd, dim3(B, cdiv_i(C, 256)), dim3(256),
+    hipLaunchKernelGGL(cond_attn_gate_fwd, dim3(B, cdiv(C, 256)), dim3(256),
                        0, stream, ctxpre_f32.data_ptr<float>(),
                        Ucon.data_ptr<float>(), Wcon.data_ptr<float>(),
                        accC.data_ptr<float>(),
@@ -1083,7 +977,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
                          (const bf16_t*)hc_bf.data_ptr(),
                          (const bf16_t*)W1pk.data_ptr(),
                          gru1_part.data_ptr<float>(), H, K1, Hpad);
-      hipLaunchKernelGGL(cond_gru1_step_pointwise, dim3(cdiv_i(B * H, 256)),
+      hipLaunchKernelGGL(cond_gru1_step_pointwise, dim3(cdiv(B * H, 256)),
                          dim3(256), 0, stream, gru1_part.data_ptr<float>(),
                          GRU1_KS, h1_all.data_ptr<float>() + (long)t * B * H,
                          b1.data_ptr<float>(), bx1.data_ptr<float>(), mt,
@@ -1132,8 +1026,8 @@ std::vector<torch::Tensor> cond_gru_bwd(
   const int A = Uatt.size(0);
   const int K3Hpad = U1cat.size(1);
   const int Apad32 = WattB.size(1);
-  const int ngrpH = cdiv_i(H, JB);
-  const int ngrpC = cdiv_i(C, JB);
+  const int ngrpH = cdiv(H, JB);
+  const int ngrpC = cdiv(C, JB);
 
   auto optsF = dh2_all.options().dtype(torch::kFloat32);
   auto optsB = dh2_all.options().dtype(torch::kBFloat16);
@@ -1169,24 +1063,10 @@ std::vector<torch::Tensor> cond_gru_bwd(
   auto dstep2 = torch::zeros({32, K3Hpad}, optsB);
   auto init_f = init_state.contiguous().to(torch::kFloat32);
 
-  const float* mask_all = nullptr;
-  torch::Tensor mask_c;
-  if (mask.has_value()) {
-    mask_c = mask->contiguous().to(torch::kFloat32);
-    mask_all = mask_c.data_ptr<float>();
-  }
-  torch::Tensor dctxs_c;
-  const float* dctxs_p = nullptr;
-  if (dctxs_all.has_value()) {
-    dctxs_c = dctxs_all->contiguous().to(torch::kFloat32);
-    dctxs_p = dctxs_c.data_ptr<float>();
-  }
-  torch::Tensor dalpha_c;
-  const float* dalpha_p = nullptr;
-  if (dalphas_all.has_value()) {
-    dalpha_c = dalphas_all->contiguous().to(torch::kFloat32);
-    dalpha_p = dalpha_c.data_ptr<float>();
-  }
+  const OptF32 mask_f(mask), dctxs_f(dctxs_all), dalpha_f(dalphas_all);
+  const float* mask_all = mask_f.p;
+  const float* dctxs_p = dctxs_f.p;
+  const float* dalpha_p = dalpha_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   auto dh2_c = dh2_all.contiguous().to(torch::kFloat32);
@@ -1237,7 +1117,7 @@ std::vector<torch::Tensor> cond_gru_bwd(
     // dot folded in (block tree + one atomic per block), then the
     // (b,s)-parallel scatter (dpctx/daccA/pc_buf) and the per-(b,i)
     // s-contiguous reduce for dpstate/dD_wei/dU_att/dc_att
-    hipLaunchKernelGGL(cond_attn_bwd_dalpha, dim3(B, cdiv_i(Ts, 4)),
+    hipLaunchKernelGGL(cond_attn_bwd_dalpha, dim3(B, cdiv(Ts, 4)),
                        dim3(256), 0, stream,
                        (const bf16_t*)ctx_bf.data_ptr(),
                        dctxpre_f32.data_ptr<float>(),
@@ -1251,7 +1131,7 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),
                        B, Ts);
     hipLaunchKernelGGL(cond_attn_bwd_scatter,
-                       dim3(B, cdiv_i(Ts, 256), A >= 32 ? 8 : (A >= 16 ? 4 : 1)),
+                       dim3(B, cdiv(Ts, 256), A >= 32 ? 8 : (A >= 16 ? 4 : 1)),
                        dim3(256), 0, stream,
                        alphas_all.data_ptr<float>() + (long)t * B * Ts,
                        dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),

@@ -5,6 +5,66 @@
 
 #include "common.h"
 
+// The GRU cell (nats.py:336-356), shared by every forward/backward site of
+// the encoder scans and both decoder GRUs. pr/pu/px are the recurrent
+// preactivations (pr, pu with their input projections already added), xc
+// the candidate's input projection, hp the previous state, mask_t the
+// step's [B] mask or null and b this element's row. GRU_1 calls it with
+// px = pxa + bx1 and xc = pxb.
+struct GruCellFwd {
+  float r, u, hbar, hnew;
+};
+
+__device__ __forceinline__ GruCellFwd gru_cell_fwd(float pr, float pu,
+                                                   float px, float xc,
+                                                   float hp,
+                                                   const float* mask_t,
+                                                   int b) {
+  const float r = nats_sigmoid(pr);
+  const float u = nats_sigmoid(pu);
+  const float hbar = tanhf(px * r + xc);
+  float hnew = u * hp + (1.f - u) * hbar;
+  if (mask_t != nullptr) {
+    const float mm = mask_t[b];
+    hnew = mm * hnew + (1.f - mm) * hp;
+  }
+  return GruCellFwd{r, u, hbar, hnew};
+}
+
+// dh -> gate-preactivation grads; mm = 1 without a mask. dpx is the grad of
+// the candidate preactivation (= dxc), dpxl = dpx * r the part that flows
+// into h@Ux, ddirect the passthrough into dh_{t-1}.
+struct GruCellBwd {
+  float dpr, dpu, dpx, dpxl, ddirect;
+};
+
+__device__ __forceinline__ GruCellBwd gru_cell_bwd(float dh, float r, float u,
+                                                   float px, float hbar,
+                                                   float hp, float mm) {
+  GruCellBwd o;
+  const float du = dh * mm * (hp - hbar);
+  const float dhbar = dh * mm * (1.f - u);
+  o.dpx = dhbar * (1.f - hbar * hbar);
+  o.dpxl = o.dpx * r;
+  const float dr = o.dpx * px;
+  o.dpr = dr * r * (1.f - r);
+  o.dpu = du * u * (1.f - u);
+  o.ddirect = dh * (mm * u + (1.f - mm));
+  return o;
+}
+
+// host: optional tensor -> contiguous fp32 copy + raw pointer (null if absent)
+struct OptF32 {
+  torch::Tensor t;
+  const float* p = nullptr;
+  explicit OptF32(const c10::optional<torch::Tensor>& o) {
+    if (o.has_value()) {
+      t = o->contiguous().to(torch::kFloat32);
+      p = t.data_ptr<float>();
+    }
+  }
+};
+
 // forward step: fused [h@U_r | h@U_u | h@Ux] MFMA + gates/mask pointwise.
 // ld_bfout = row stride of the bf16 h output (lets the decoder write h1
 // into the [h1|ctx] packed GRU_1 operand buffer).

@@ -34,11 +34,43 @@
 #include "common.h"
 #include "gru_kernels.h"
 
-static constexpr int JB = 16;  // output columns per workgroup
-
 // ---------------- forward step ----------------
 // block: 384 threads = 6 waves; wave w -> (m = w/3, g = w%3) computes the
 // 16x16 tile rows [16m,16m+16) of matrix g (0=r,1=u,2=cand).
+__device__ __forceinline__ void gru_fwd_body(const GruFwdArgs& a,
+                                             int ld_bfout, int B, int H,
+                                             int Hpad, int wg) {
+  __shared__ float pre[3][32][JB + 1];
+  const int wave = threadIdx.x / NATS_WAVE;
+  const int m = wave / 3;
+  const int g = wave % 3;
+  const int j0 = wg * JB;
+
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const bf16_t* brow = a.Upk + (long)(wg * 3 + g) * JB * Hpad;
+  NATS_MFMA_KLOOP(acc, a.h_bf, 16 * m, Hpad, brow, 0, Hpad, 0, Hpad);
+  store_cd_lds(pre[g], acc, 16 * m);
+  __syncthreads();
+
+  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
+    const int b = idx / JB;
+    const int c = idx % JB;
+    const int j = j0 + c;
+    if (j >= H) continue;
+    const float hp = a.h_prev[(long)b * H + j];
+    const float pr = pre[0][b][c] + (float)a.xg_t[(long)b * 2 * H + j];
+    const float pu = pre[1][b][c] + (float)a.xg_t[(long)b * 2 * H + H + j];
+    const float px = pre[2][b][c];
+    const GruCellFwd o = gru_cell_fwd(
+        pr, pu, px, (float)a.xc_t[(long)b * H + j], hp, a.mask_t, b);
+    a.h_out[(long)b * H + j] = o.hnew;
+    a.h_bf_out[(long)b * ld_bfout + j] = (bf16_t)o.hnew;
+    a.saved_t[(long)b * 3 * H + j] = (bf16_t)o.r;
+    a.saved_t[(long)b * 3 * H + H + j] = (bf16_t)o.u;
+    a.saved_t[(long)b * 3 * H + 2 * H + j] = (bf16_t)px;
+  }
+}
+
 __global__ __launch_bounds__(384) void nats_gru_step_fwd(
     const bf16_t* __restrict__ h_bf,   // [32][Hpad] current h (bf16)
     const float* __restrict__ h_prev,  // [B][H] fp32 (= h_all[t-1] or h0)
@@ -51,49 +83,15 @@ __global__ __launch_bounds__(384) void nats_gru_step_fwd(
     int ld_bfout,
     bf16_t* __restrict__ saved_t,      // [B][3H] (r,u,pxl) at step t
     int B, int H, int Hpad) {
-  __shared__ float pre[3][32][JB + 1];
+  gru_fwd_body(GruFwdArgs{h_bf, h_prev, Upk, xg_t, xc_t, mask_t, h_out,
+                          h_bf_out, saved_t},
+               ld_bfout, B, H, Hpad, blockIdx.x);
+}
 
-  const int wg = blockIdx.x;
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 3;
-  const int g = wave % 3;
-  const int j0 = wg * JB;
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const bf16_t* brow = Upk + (long)(wg * 3 + g) * JB * Hpad;
-  NATS_MFMA_KLOOP(acc, h_bf, 16 * m, Hpad, brow, 0, Hpad, 0, Hpad);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pre[g][rbase + i][col] = acc[i];
-  }
-  __syncthreads();
-
-  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
-    const int b = idx / JB;
-    const int c = idx % JB;
-    const int j = j0 + c;
-    if (j >= H) continue;
-    const float hp = h_prev[(long)b * H + j];
-    const float pr = pre[0][b][c] + (float)xg_t[(long)b * 2 * H + j];
-    const float pu = pre[1][b][c] + (float)xg_t[(long)b * 2 * H + H + j];
-    const float px = pre[2][b][c];
-    const float r = nats_sigmoid(pr);
-    const float u = nats_sigmoid(pu);
-    const float hbar = tanhf(px * r + (float)xc_t[(long)b * H + j]);
-    float hnew = u * hp + (1.f - u) * hbar;
-    if (mask_t != nullptr) {
-      const float mm = mask_t[b];
-      hnew = mm * hnew + (1.f - mm) * hp;
-    }
-    h_out[(long)b * H + j] = hnew;
-    h_bf_out[(long)b * ld_bfout + j] = (bf16_t)hnew;
-    saved_t[(long)b * 3 * H + j] = (bf16_t)r;
-    saved_t[(long)b * 3 * H + H + j] = (bf16_t)u;
-    saved_t[(long)b * 3 * H + 2 * H + j] = (bf16_t)px;
-  }
+// one launch per timestep covers both directions (blockIdx.y)
+__global__ __launch_bounds__(384) void nats_gru_step_fwd_bidir(
+    GruFwdArgs a0, GruFwdArgs a1, int ld_bfout, int B, int H, int Hpad) {
+  gru_fwd_body(blockIdx.y == 0 ? a0 : a1, ld_bfout, B, H, Hpad, blockIdx.x);
 }
 
 // ---------------- forward step, split-K (decoder GRU_2) ----------------
@@ -152,18 +150,12 @@ __global__ void nats_gru2_step_pointwise(
     const float pr = p0 + (float)xg_t[(long)b * 2 * H + j];
     const float pu = p1 + (float)xg_t[(long)b * 2 * H + H + j];
     const float px = p2;
-    const float r = nats_sigmoid(pr);
-    const float u = nats_sigmoid(pu);
-    const float hbar = tanhf(px * r + (float)xc_t[idx]);
-    float hnew = u * hp + (1.f - u) * hbar;
-    if (mask_t != nullptr) {
-      const float mm = mask_t[b];
-      hnew = mm * hnew + (1.f - mm) * hp;
-    }
-    h_out[idx] = hnew;
-    h_bf_out[(long)b * ld_bfout + j] = (bf16_t)hnew;
-    saved_t[(long)b * 3 * H + j] = (bf16_t)r;
-    saved_t[(long)b * 3 * H + H + j] = (bf16_t)u;
+    const GruCellFwd o =
+        gru_cell_fwd(pr, pu, px, (float)xc_t[idx], hp, mask_t, b);
+    h_out[idx] = o.hnew;
+    h_bf_out[(long)b * ld_bfout + j] = (bf16_t)o.hnew;
+    saved_t[(long)b * 3 * H + j] = (bf16_t)o.r;
+    saved_t[(long)b * 3 * H + H + j] = (bf16_t)o.u;
     saved_t[(long)b * 3 * H + 2 * H + j] = (bf16_t)px;
   }
 }
@@ -194,74 +186,16 @@ __global__ void nats_gru_step_bwd_pointwise(
     const float hbar = tanhf(px * r + (float)xc_t[idx]);
     const float hp = h_prev[idx];
     const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-    const float du = dh * mm * (hp - hbar);
-    const float dhbar = dh * mm * (1.f - u);
-    const float dpx = dhbar * (1.f - hbar * hbar);  // = dxc
-    const float dpxl = dpx * r;
-    const float dr = dpx * px;
-    const float dpr = dr * r * (1.f - r);
-    const float dpu = du * u * (1.f - u);
-    ddirect[idx] = dh * (mm * u + (1.f - mm));
-    dstep[(long)b * ld_dstep + j] = (bf16_t)dpr;
-    dstep[(long)b * ld_dstep + H + j] = (bf16_t)dpu;
-    dstep[(long)b * ld_dstep + 2 * H + j] = (bf16_t)dpxl;
-    dpre_t[(long)b * 4 * H + j] = (bf16_t)dpr;
-    dpre_t[(long)b * 4 * H + H + j] = (bf16_t)dpu;
-    dpre_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)dpx;
-    dpre_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)dpxl;
+    const GruCellBwd o = gru_cell_bwd(dh, r, u, px, hbar, hp, mm);
+    ddirect[idx] = o.ddirect;
+    dstep[(long)b * ld_dstep + j] = (bf16_t)o.dpr;
+    dstep[(long)b * ld_dstep + H + j] = (bf16_t)o.dpu;
+    dstep[(long)b * ld_dstep + 2 * H + j] = (bf16_t)o.dpxl;
+    dpre_t[(long)b * 4 * H + j] = (bf16_t)o.dpr;
+    dpre_t[(long)b * 4 * H + H + j] = (bf16_t)o.dpu;
+    dpre_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)o.dpx;
+    dpre_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.dpxl;
   }
-}
-
-// ---------------- bidirectional forward step ----------------
-__device__ __forceinline__ void gru_fwd_body(const GruFwdArgs& a,
-                                             int ld_bfout, int B, int H,
-                                             int Hpad, int wg) {
-  __shared__ float pre[3][32][JB + 1];
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 3;
-  const int g = wave % 3;
-  const int j0 = wg * JB;
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const bf16_t* brow = a.Upk + (long)(wg * 3 + g) * JB * Hpad;
-  NATS_MFMA_KLOOP(acc, a.h_bf, 16 * m, Hpad, brow, 0, Hpad, 0, Hpad);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pre[g][rbase + i][col] = acc[i];
-  }
-  __syncthreads();
-
-  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
-    const int b = idx / JB;
-    const int c = idx % JB;
-    const int j = j0 + c;
-    if (j >= H) continue;
-    const float hp = a.h_prev[(long)b * H + j];
-    const float pr = pre[0][b][c] + (float)a.xg_t[(long)b * 2 * H + j];
-    const float pu = pre[1][b][c] + (float)a.xg_t[(long)b * 2 * H + H + j];
-    const float px = pre[2][b][c];
-    const float r = nats_sigmoid(pr);
-    const float u = nats_sigmoid(pu);
-    const float hbar = tanhf(px * r + (float)a.xc_t[(long)b * H + j]);
-    float hnew = u * hp + (1.f - u) * hbar;
-    if (a.mask_t != nullptr) {
-      const float mm = a.mask_t[b];
-      hnew = mm * hnew + (1.f - mm) * hp;
-    }
-    a.h_out[(long)b * H + j] = hnew;
-    a.h_bf_out[(long)b * ld_bfout + j] = (bf16_t)hnew;
-    a.saved_t[(long)b * 3 * H + j] = (bf16_t)r;
-    a.saved_t[(long)b * 3 * H + H + j] = (bf16_t)u;
-    a.saved_t[(long)b * 3 * H + 2 * H + j] = (bf16_t)px;
-  }
-}
-
-__global__ __launch_bounds__(384) void nats_gru_step_fwd_bidir(
-    GruFwdArgs a0, GruFwdArgs a1, int ld_bfout, int B, int H, int Hpad) {
-  gru_fwd_body(blockIdx.y == 0 ? a0 : a1, ld_bfout, B, H, Hpad, blockIdx.x);
 }
 
 // ---------------- fused backward step (gemm of t+1's dstep + pointwise)
@@ -280,13 +214,7 @@ __device__ __forceinline__ void gru_bwd_fused_body(const GruBwdArgs& a,
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   NATS_MFMA_KLOOP(acc, a.dstep_in, 16 * m, Kpad, Ubwd, i0, Kpad, kbeg, kend);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(part[ks], acc, 16 * m);
   __syncthreads();
 
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
@@ -305,21 +233,15 @@ __device__ __forceinline__ void gru_bwd_fused_body(const GruBwdArgs& a,
     const float hbar = tanhf(px * r + (float)a.xc_t[bj]);
     const float hp = a.h_prev[bj];
     const float mm = (a.mask_t != nullptr) ? a.mask_t[b] : 1.f;
-    const float du = dh * mm * (hp - hbar);
-    const float dhbar = dh * mm * (1.f - u);
-    const float dpx = dhbar * (1.f - hbar * hbar);
-    const float dpxl = dpx * r;
-    const float dr = dpx * px;
-    const float dpr = dr * r * (1.f - r);
-    const float dpu = du * u * (1.f - u);
-    a.ddirect_out[bj] = dh * (mm * u + (1.f - mm));
-    a.dstep_out[(long)b * Kpad + j] = (bf16_t)dpr;
-    a.dstep_out[(long)b * Kpad + H + j] = (bf16_t)dpu;
-    a.dstep_out[(long)b * Kpad + 2 * H + j] = (bf16_t)dpxl;
-    a.dpre_t[(long)b * 4 * H + j] = (bf16_t)dpr;
-    a.dpre_t[(long)b * 4 * H + H + j] = (bf16_t)dpu;
-    a.dpre_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)dpx;
-    a.dpre_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)dpxl;
+    const GruCellBwd o = gru_cell_bwd(dh, r, u, px, hbar, hp, mm);
+    a.ddirect_out[bj] = o.ddirect;
+    a.dstep_out[(long)b * Kpad + j] = (bf16_t)o.dpr;
+    a.dstep_out[(long)b * Kpad + H + j] = (bf16_t)o.dpu;
+    a.dstep_out[(long)b * Kpad + 2 * H + j] = (bf16_t)o.dpxl;
+    a.dpre_t[(long)b * 4 * H + j] = (bf16_t)o.dpr;
+    a.dpre_t[(long)b * 4 * H + H + j] = (bf16_t)o.dpu;
+    a.dpre_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)o.dpx;
+    a.dpre_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.dpxl;
   }
 }
 
@@ -691,13 +613,7 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_fwd(
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     NATS_MFMA_KLOOP_LDSB(acc, h_bf_in, 16 * m, Hpad, upk_lds, g * JB, Hpad,
                          0, Hpad);
-    {
-      const int lane = threadIdx.x & (NATS_WAVE - 1);
-      const int col = lane & 15;
-      const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) pre[g][rbase + i][col] = acc[i];
-    }
+    store_cd_lds(pre[g], acc, 16 * m);
     __syncthreads();
 
     const float* mask_t = p.mask ? p.mask + (long)t * p.smask : nullptr;
@@ -713,19 +629,13 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_fwd(
       const float pr = pre[0][b][c] + pf_xr[it];
       const float pu = pre[1][b][c] + pf_xu[it];
       const float px = pre[2][b][c];
-      const float r = nats_sigmoid(pr);
-      const float u = nats_sigmoid(pu);
-      const float hbar = tanhf(px * r + pf_xc[it]);
-      float hnew = u * hp + (1.f - u) * hbar;
-      if (mask_t != nullptr) {
-        const float mm = mask_t[b];
-        hnew = mm * hnew + (1.f - mm) * hp;
-      }
-      h_keep[it] = hnew;
-      h_out[(long)b * H + j] = hnew;
-      h_bf_out[(long)b * Hpad + j] = (bf16_t)hnew;
-      pend_r[it] = r;
-      pend_u[it] = u;
+      const GruCellFwd o =
+          gru_cell_fwd(pr, pu, px, pf_xc[it], hp, mask_t, b);
+      h_keep[it] = o.hnew;
+      h_out[(long)b * H + j] = o.hnew;
+      h_bf_out[(long)b * Hpad + j] = (bf16_t)o.hnew;
+      pend_r[it] = o.r;
+      pend_u[it] = o.u;
       pend_px[it] = px;
     }
     pend_saved = p.saved + (long)t * p.ssaved;
@@ -858,13 +768,7 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_bwd(
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     NATS_MFMA_KLOOP_LDSB(acc, dstep_in, 16 * m, K3pad, ub_lds, 0, K3pad,
                          kbeg, kend);
-    {
-      const int lane = threadIdx.x & (NATS_WAVE - 1);
-      const int col = lane & 15;
-      const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) part[ks][rbase + i][col] = acc[i];
-    }
+    store_cd_lds(part[ks], acc, 16 * m);
     __syncthreads();
 
     const float* mask_t = p.mask ? p.mask + (long)t * p.smask : nullptr;
@@ -884,23 +788,16 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_bwd(
       const float hbar = tanhf(px * r + pf_xc[it]);
       const float hp = pf_hp[it];
       const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-      const float du = dh * mm * (hp - hbar);
-      const float dhbar = dh * mm * (1.f - u);
-      const float dpx = dhbar * (1.f - hbar * hbar);
-      const float dpxl = dpx * r;
-      const float dr = dpx * px;
-      const float dpr = dr * r * (1.f - r);
-      const float dpu = du * u * (1.f - u);
-      const float dd = dh * (mm * u + (1.f - mm));
-      dd_keep[it] = dd;
-      p.ddirect[bj] = dd;
-      dstep_out[(long)b * K3pad + j] = (bf16_t)dpr;
-      dstep_out[(long)b * K3pad + H + j] = (bf16_t)dpu;
-      dstep_out[(long)b * K3pad + 2 * H + j] = (bf16_t)dpxl;
-      pend[it][0] = dpr;
-      pend[it][1] = dpu;
-      pend[it][2] = dpx;
-      pend[it][3] = dpxl;
+      const GruCellBwd o = gru_cell_bwd(dh, r, u, px, hbar, hp, mm);
+      dd_keep[it] = o.ddirect;
+      p.ddirect[bj] = o.ddirect;
+      dstep_out[(long)b * K3pad + j] = (bf16_t)o.dpr;
+      dstep_out[(long)b * K3pad + H + j] = (bf16_t)o.dpu;
+      dstep_out[(long)b * K3pad + 2 * H + j] = (bf16_t)o.dpxl;
+      pend[it][0] = o.dpr;
+      pend[it][1] = o.dpu;
+      pend[it][2] = o.dpx;
+      pend[it][3] = o.dpxl;
     }
     pend_dpre = p.dpre + (long)t * p.sdpre;
     have_pend = true;
@@ -948,13 +845,7 @@ __global__ __launch_bounds__(384) void nats_gru_step_bwd_gemm(
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   NATS_MFMA_KLOOP(acc, dstep, 16 * m, Kpad, Wt, i0, Kpad, kbeg, kend);
-  {
-    const int lane = threadIdx.x & (NATS_WAVE - 1);
-    const int col = lane & 15;
-    const int rbase = 16 * m + (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) part[ks][rbase + i][col] = acc[i];
-  }
+  store_cd_lds(part[ks], acc, 16 * m);
   __syncthreads();
 
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
@@ -969,8 +860,6 @@ __global__ __launch_bounds__(384) void nats_gru_step_bwd_gemm(
 
 
 // ---------------- host drivers ----------------
-
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 std::vector<torch::Tensor> gru_scan_fwd(torch::Tensor xg, torch::Tensor xc,
                                         c10::optional<torch::Tensor> mask,
@@ -1000,12 +889,8 @@ std::vector<torch::Tensor> gru_scan_fwd(torch::Tensor xg, torch::Tensor xc,
   } else {
     hprev0 = torch::zeros({B, H}, optsF);
   }
-  const float* mask_p = nullptr;
-  torch::Tensor mask_c;
-  if (mask.has_value()) {
-    mask_c = mask->contiguous().to(torch::kFloat32);
-    mask_p = mask_c.data_ptr<float>();
-  }
+  const OptF32 mask_f(mask);
+  const float* mask_p = mask_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   const bf16_t* xg_p = (const bf16_t*)xg.data_ptr();
@@ -1031,8 +916,52 @@ std::vector<torch::Tensor> gru_scan_fwd(torch::Tensor xg, torch::Tensor xc,
   return {h_all, saved};
 }
 
-// Bidirectional encoder forward: one launch per timestep covers both
-// directions (grid.y = direction). h0 = 0 (nats.py:360).
+// ---------------- persistent-scan plan ----------------
+// Both persistent kernels launch this many blocks; every (job, column-tile)
+// slot needs a block of its own, all resident at once.
+constexpr int NATS_PERSIST_GRID = 256;
+constexpr size_t NATS_PERSIST_SMEM_MAX = 150 * 1024;  // >= 1 block per CU
+
+// The one place that decides whether (H, B) runs on the persistent scans
+// and with which geometry: jobs = directions x 32-row batch chunks
+// (B <= 64), all concurrent in ONE launch with per-job barriers — a 64-row
+// batch costs the same T barrier intervals as a 32-row one instead of 2x.
+struct GruPersistPlan {
+  bool ok;
+  int ngrp, njobs;
+  int xpd;  // preferred XCDs per job (nats_claim_job_slot)
+  size_t smem_fwd, smem_bwd;
+};
+
+static GruPersistPlan gru_persist_plan(int H, int B) {
+  GruPersistPlan p;
+  const size_t Hpad = cdiv(H, 32) * 32, K3pad = cdiv(3 * H, 32) * 32;
+  const size_t tiles = sizeof(float) * 3 * 32 * (JB + 1);
+  p.ngrp = cdiv(H, JB);
+  p.njobs = 2 * cdiv(B, 32);
+  p.smem_fwd = 3 * JB * Hpad * 2 + tiles;  // [3*16][Hpad] bf16 + pre
+  p.smem_bwd = JB * K3pad * 2 + tiles;     // [16][K3pad] bf16 + part
+  // 2 XCDs (64 CUs) per job when its grid fits comfortably (LCSTS
+  // ngrp=32: +2.5% measured); 4 when 63 WGs would sit 1/CU
+  const char* xpd_env = getenv("NATS_XPD");
+  p.xpd = xpd_env ? atoi(xpd_env)
+                  : (p.njobs == 4 ? 2 : (p.ngrp <= 48 ? 2 : 4));
+  p.ok = p.njobs <= 4 && 2 * p.ngrp <= 192 &&
+         p.njobs * p.ngrp <= NATS_PERSIST_GRID &&
+         p.smem_fwd <= NATS_PERSIST_SMEM_MAX &&
+         p.smem_bwd <= NATS_PERSIST_SMEM_MAX &&
+         getenv("NATS_NO_PERSISTENT") == nullptr;
+  return p;
+}
+
+// Can the persistent bidirectional scans take this hidden size and batch?
+bool gru_persistent_ok(long H, long B) {
+  return gru_persist_plan((int)H, (int)B).ok;
+}
+
+// Bidirectional encoder forward: the persistent launch when the plan
+// allows it, else one launch per timestep covering both directions
+// (grid.y = direction). h0 = 0 (nats.py:360).
 std::vector<torch::Tensor> gru_scan_fwd_bidir(
     torch::Tensor xg0, torch::Tensor xc0, c10::optional<torch::Tensor> mask0,
     torch::Tensor Upk0, torch::Tensor xg1, torch::Tensor xc1,
@@ -1040,127 +969,87 @@ std::vector<torch::Tensor> gru_scan_fwd_bidir(
   const int T = xg0.size(0), B = xg0.size(1), H = xc0.size(2);
   TORCH_CHECK(B <= 64, "bidir gru_scan: batch must be <= 64");
   const int Hpad = Upk0.size(1);
-  const int ngrp = cdiv(H, JB);
+  const GruPersistPlan plan = gru_persist_plan(H, B);
+  const int ngrp = plan.ngrp;
 
   auto optsF = xg0.options().dtype(torch::kFloat32);
   auto optsB = xg0.options();
-  auto h_all0 = torch::empty({T, B, H}, optsF);
-  auto h_all1 = torch::empty({T, B, H}, optsF);
-  auto saved0 = torch::empty({T, B, 3 * H}, optsB);
-  auto saved1 = torch::empty({T, B, 3 * H}, optsB);
-  auto h_bf = torch::zeros({2, 2, 32, Hpad}, optsB);  // [dir][pingpong]
+  const torch::Tensor xg[2] = {xg0, xg1}, xc[2] = {xc0, xc1};
+  const torch::Tensor Upk[2] = {Upk0, Upk1};
+  const OptF32 mask[2] = {OptF32(mask0), OptF32(mask1)};
+  torch::Tensor h_all[2], saved[2];
+  for (int d = 0; d < 2; ++d) {
+    h_all[d] = torch::empty({T, B, H}, optsF);
+    saved[d] = torch::empty({T, B, 3 * H}, optsB);
+  }
   auto h00 = torch::zeros({B, H}, optsF);
-
-  const float* m0 = nullptr;
-  const float* m1 = nullptr;
-  torch::Tensor m0c, m1c;
-  if (mask0.has_value()) {
-    m0c = mask0->contiguous().to(torch::kFloat32);
-    m0 = m0c.data_ptr<float>();
-  }
-  if (mask1.has_value()) {
-    m1c = mask1->contiguous().to(torch::kFloat32);
-    m1 = m1c.data_ptr<float>();
-  }
-
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   const long hb = (long)32 * Hpad;
-  bf16_t* hbf = (bf16_t*)h_bf.data_ptr();
 
-  // persistent path: weight slices LDS-resident across all T steps
-  const size_t smem_fwd =
-      (size_t)3 * JB * Hpad * 2 + sizeof(float) * 3 * 32 * (JB + 1);
-  const bool persistent = (2 * ngrp <= 192) && (smem_fwd <= 150 * 1024) &&
-                          (getenv("NATS_NO_PERSISTENT") == nullptr);
-  if (persistent) {
-    // jobs = directions x 32-row batch chunks (B <= 64), all concurrent
-    // in ONE launch with per-job barriers — a 64-row batch costs the
-    // same T barrier intervals as a 32-row one instead of 2x
-    const int nchunk = cdiv(B, 32);
-    TORCH_CHECK(nchunk <= 2, "persistent bidir scan: B must be <= 64");
-    const int njobs = 2 * nchunk;
+  if (plan.ok) {  // weight slices LDS-resident across all T steps
+    const int njobs = plan.njobs;
     auto sync = torch::zeros({njobs * NATS_SYNC_WORDS + 8},
                              xg0.options().dtype(torch::kInt32));
-    unsigned* sync_p = (unsigned*)sync.data_ptr<int>();
     auto h_bfj = torch::zeros({njobs, 2, 32, Hpad}, optsB);
-    bf16_t* hbfj = (bf16_t*)h_bfj.data_ptr();
     GruPersistFwd jobs[4];
     for (int j = 0; j < njobs; ++j) {
-      const int dir = j & 1;            // interleave so chunk pairs of a
-      const int ch = j >> 1;            // direction sit on far XCD sets
-      const int a = ch * 32;
-      const int Bj = std::min(32, B - a);
-      const torch::Tensor& xg = dir == 0 ? xg0 : xg1;
-      const torch::Tensor& xc = dir == 0 ? xc0 : xc1;
-      const torch::Tensor& Upk = dir == 0 ? Upk0 : Upk1;
-      torch::Tensor& h_all = dir == 0 ? h_all0 : h_all1;
-      torch::Tensor& saved = dir == 0 ? saved0 : saved1;
-      const float* mj = dir == 0 ? m0 : m1;
+      const int d = j & 1;         // interleave so chunk pairs of a
+      const int a = (j >> 1) * 32; // direction sit on far XCD sets
       jobs[j] = GruPersistFwd{
-          (const bf16_t*)xg.data_ptr() + (long)a * 2 * H,
-          (const bf16_t*)xc.data_ptr() + (long)a * H,
-          mj ? mj + a : nullptr,
-          (const bf16_t*)Upk.data_ptr(),
-          h_all.data_ptr<float>() + (long)a * H,
-          hbfj + (long)j * 2 * hb,
-          (bf16_t*)saved.data_ptr() + (long)a * 3 * H,
+          (const bf16_t*)xg[d].data_ptr() + (long)a * 2 * H,
+          (const bf16_t*)xc[d].data_ptr() + (long)a * H,
+          mask[d].p ? mask[d].p + a : nullptr,
+          (const bf16_t*)Upk[d].data_ptr(),
+          h_all[d].data_ptr<float>() + (long)a * H,
+          (bf16_t*)h_bfj.data_ptr() + (long)j * 2 * hb,
+          (bf16_t*)saved[d].data_ptr() + (long)a * 3 * H,
           h00.data_ptr<float>() + (long)a * H,
-          Bj,
+          std::min(32, B - a),
           (long)B * 2 * H, (long)B * H, (long)B, (long)B * H,
           (long)B * 3 * H};
     }
     for (int j = njobs; j < 4; ++j) jobs[j] = jobs[0];
     const int unsafe = getenv("NATS_UNSAFE_NOBARRIER") != nullptr;
     // overprovisioned 1-D grid: blocks self-select a (job, tile) slot
-    // with XCD preference (see nats_claim_job_slot); all 256 fit
-    // resident (smem gate is 150KB -> >=1 block/CU)
-    const char* xpd_env = getenv("NATS_XPD");
-    // 2 XCDs (64 CUs) per job when its grid fits comfortably (LCSTS
-    // ngrp=32: +2.5% measured); 4 when 63 WGs would sit 1/CU
-    const int xpd = xpd_env ? atoi(xpd_env)
-                            : (njobs == 4 ? 2 : (ngrp <= 48 ? 2 : 4));
-    hipLaunchKernelGGL(nats_gru_persistent_fwd, dim3(256), dim3(384),
-                       smem_fwd, stream, jobs[0], jobs[1], jobs[2], jobs[3],
-                       T, H, Hpad, sync_p, ngrp, njobs, xpd, unsafe);
+    // with XCD preference (see nats_claim_job_slot)
+    hipLaunchKernelGGL(nats_gru_persistent_fwd, dim3(NATS_PERSIST_GRID),
+                       dim3(384), plan.smem_fwd, stream, jobs[0], jobs[1],
+                       jobs[2], jobs[3], T, H, Hpad,
+                       (unsigned*)sync.data_ptr<int>(), ngrp, njobs, plan.xpd,
+                       unsafe);
     HIP_CHECK(hipGetLastError());
-    return {h_all0, saved0, h_all1, saved1};
+    return {h_all[0], saved[0], h_all[1], saved[1]};
   }
 
   TORCH_CHECK(B <= 32,
               "bidir scan: B > 32 requires the persistent path "
               "(gru_persistent_ok)");
+  auto h_bf = torch::zeros({2, 2, 32, Hpad}, optsB);  // [dir][pingpong]
+  bf16_t* hbf = (bf16_t*)h_bf.data_ptr();
   for (int t = 0; t < T; ++t) {
-    GruFwdArgs a0{
-        hbf + 0 * 2 * hb + (t % 2) * hb,
-        (t == 0) ? h00.data_ptr<float>()
-                 : h_all0.data_ptr<float>() + (long)(t - 1) * B * H,
-        (const bf16_t*)Upk0.data_ptr(),
-        (const bf16_t*)xg0.data_ptr() + (long)t * B * 2 * H,
-        (const bf16_t*)xc0.data_ptr() + (long)t * B * H,
-        m0 ? m0 + (long)t * B : nullptr,
-        h_all0.data_ptr<float>() + (long)t * B * H,
-        hbf + 0 * 2 * hb + ((t + 1) % 2) * hb,
-        (bf16_t*)saved0.data_ptr() + (long)t * B * 3 * H};
-    GruFwdArgs a1{
-        hbf + 1 * 2 * hb + (t % 2) * hb,
-        (t == 0) ? h00.data_ptr<float>()
-                 : h_all1.data_ptr<float>() + (long)(t - 1) * B * H,
-        (const bf16_t*)Upk1.data_ptr(),
-        (const bf16_t*)xg1.data_ptr() + (long)t * B * 2 * H,
-        (const bf16_t*)xc1.data_ptr() + (long)t * B * H,
-        m1 ? m1 + (long)t * B : nullptr,
-        h_all1.data_ptr<float>() + (long)t * B * H,
-        hbf + 1 * 2 * hb + ((t + 1) % 2) * hb,
-        (bf16_t*)saved1.data_ptr() + (long)t * B * 3 * H};
+    auto args = [&](int d) {
+      float* h = h_all[d].data_ptr<float>();
+      return GruFwdArgs{
+          hbf + (2 * d + t % 2) * hb,
+          (t == 0) ? h00.data_ptr<float>() : h + (long)(t - 1) * B * H,
+          (const bf16_t*)Upk[d].data_ptr(),
+          (const bf16_t*)xg[d].data_ptr() + (long)t * B * 2 * H,
+          (const bf16_t*)xc[d].data_ptr() + (long)t * B * H,
+          mask[d].p ? mask[d].p + (long)t * B : nullptr,
+          h + (long)t * B * H,
+          hbf + (2 * d + (t + 1) % 2) * hb,
+          (bf16_t*)saved[d].data_ptr() + (long)t * B * 3 * H};
+    };
     hipLaunchKernelGGL(nats_gru_step_fwd_bidir, dim3(ngrp, 2), dim3(384), 0,
-                       stream, a0, a1, Hpad, B, H, Hpad);
+                       stream, args(0), args(1), Hpad, B, H, Hpad);
   }
   HIP_CHECK(hipGetLastError());
-  return {h_all0, saved0, h_all1, saved1};
+  return {h_all[0], saved[0], h_all[1], saved[1]};
 }
 
-// Bidirectional fused backward: one launch per timestep (both directions,
-// gemm-of-previous-dstep + pointwise fused, SURVEY §2.4 backward of K3).
+// Bidirectional backward: the persistent launch, else one fused launch per
+// timestep (both directions, gemm-of-previous-dstep + pointwise, SURVEY
+// §2.4 backward of K3); then dh0 = ddirect(0) + dstep(0) @ Ubwd^T.
 std::vector<torch::Tensor> gru_scan_bwd_bidir(
     torch::Tensor dh_out0, torch::Tensor h_all0, torch::Tensor saved0,
     torch::Tensor xc0, c10::optional<torch::Tensor> mask0,
@@ -1169,148 +1058,102 @@ std::vector<torch::Tensor> gru_scan_bwd_bidir(
     c10::optional<torch::Tensor> mask1, torch::Tensor Ubwd1) {
   const int T = dh_out0.size(0), B = dh_out0.size(1), H = dh_out0.size(2);
   const int K3pad = Ubwd0.size(1);
-  const int ngrp = cdiv(H, JB);
+  const GruPersistPlan plan = gru_persist_plan(H, B);
+  const int ngrp = plan.ngrp;
 
   auto optsF = dh_out0.options();
   auto optsB = dh_out0.options().dtype(torch::kBFloat16);
-  auto dpre0 = torch::empty({T, B, 4 * H}, optsB);
-  auto dpre1 = torch::empty({T, B, 4 * H}, optsB);
-  auto ddir = torch::zeros({2, B, H}, optsF);
-  auto dstep = torch::zeros({2, 2, 32, K3pad}, optsB);  // [dir][pingpong]
+  const torch::Tensor h_all[2] = {h_all0, h_all1}, saved[2] = {saved0, saved1};
+  const torch::Tensor xc[2] = {xc0, xc1}, Ubwd[2] = {Ubwd0, Ubwd1};
+  const torch::Tensor dhc[2] = {dh_out0.contiguous().to(torch::kFloat32),
+                                dh_out1.contiguous().to(torch::kFloat32)};
+  const OptF32 mask[2] = {OptF32(mask0), OptF32(mask1)};
+  torch::Tensor dpre[2], dh0[2];
+  for (int d = 0; d < 2; ++d) {
+    dpre[d] = torch::empty({T, B, 4 * H}, optsB);
+    dh0[d] = torch::empty({B, H}, optsF);
+  }
   auto h00 = torch::zeros({B, H}, optsF);
-  auto dh0_0 = torch::empty({B, H}, optsF);
-  auto dh0_1 = torch::empty({B, H}, optsF);
-
-  const float* m0 = nullptr;
-  const float* m1 = nullptr;
-  torch::Tensor m0c, m1c;
-  if (mask0.has_value()) {
-    m0c = mask0->contiguous().to(torch::kFloat32);
-    m0 = m0c.data_ptr<float>();
-  }
-  if (mask1.has_value()) {
-    m1c = mask1->contiguous().to(torch::kFloat32);
-    m1 = m1c.data_ptr<float>();
-  }
-
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   const long ds = (long)32 * K3pad;
+
+  // one job per (direction, 32-row chunk) on the persistent path, one per
+  // direction on the per-step path; each owns a dstep ping-pong pair and a
+  // ddirect slab of ddstride floats
+  const int njobs = plan.ok ? plan.njobs : 2;
+  const long ddstride = plan.ok ? (long)32 * H : (long)B * H;
+  auto dstep = torch::zeros({njobs, 2, 32, K3pad}, optsB);
+  auto ddir = torch::zeros({njobs * ddstride}, optsF);
   bf16_t* dsp = (bf16_t*)dstep.data_ptr();
   float* dd = ddir.data_ptr<float>();
-  auto dh0c = dh_out0.contiguous().to(torch::kFloat32);
-  auto dh1c = dh_out1.contiguous().to(torch::kFloat32);
 
-  const size_t smem_bwd =
-      (size_t)JB * K3pad * 2 + sizeof(float) * 3 * 32 * (JB + 1);
-  const bool persistent = (2 * ngrp <= 192) && (smem_bwd <= 150 * 1024) &&
-                          (getenv("NATS_NO_PERSISTENT") == nullptr);
-  if (persistent) {
-    const int nchunk = cdiv(B, 32);
-    TORCH_CHECK(nchunk <= 2, "persistent bidir scan: B must be <= 64");
-    const int njobs = 2 * nchunk;
+  if (plan.ok) {
     auto sync = torch::zeros({njobs * NATS_SYNC_WORDS + 8},
                              dh_out0.options().dtype(torch::kInt32));
-    unsigned* sync_p = (unsigned*)sync.data_ptr<int>();
-    auto dstepj = torch::zeros({njobs, 2, 32, K3pad}, optsB);
-    auto ddirj = torch::zeros({njobs, 32, H}, optsF);
-    bf16_t* dspj = (bf16_t*)dstepj.data_ptr();
-    float* ddj = ddirj.data_ptr<float>();
     GruPersistBwd jobs[4];
     for (int j = 0; j < njobs; ++j) {
-      const int dir = j & 1;
-      const int ch = j >> 1;
-      const int a = ch * 32;
-      const int Bj = std::min(32, B - a);
-      const torch::Tensor& dhc = dir == 0 ? dh0c : dh1c;
-      const torch::Tensor& h_all = dir == 0 ? h_all0 : h_all1;
-      const torch::Tensor& saved = dir == 0 ? saved0 : saved1;
-      const torch::Tensor& xc = dir == 0 ? xc0 : xc1;
-      const torch::Tensor& Ubwd = dir == 0 ? Ubwd0 : Ubwd1;
-      torch::Tensor& dpre = dir == 0 ? dpre0 : dpre1;
-      const float* mj = dir == 0 ? m0 : m1;
+      const int d = j & 1;
+      const int a = (j >> 1) * 32;
       jobs[j] = GruPersistBwd{
-          dhc.data_ptr<float>() + (long)a * H,
-          h_all.data_ptr<float>() + (long)a * H,
-          (const bf16_t*)saved.data_ptr() + (long)a * 3 * H,
-          (const bf16_t*)xc.data_ptr() + (long)a * H,
-          mj ? mj + a : nullptr,
-          (const bf16_t*)Ubwd.data_ptr(),
-          dspj + (long)j * 2 * ds,
-          ddj + (long)j * 32 * H,
-          (bf16_t*)dpre.data_ptr() + (long)a * 4 * H,
+          dhc[d].data_ptr<float>() + (long)a * H,
+          h_all[d].data_ptr<float>() + (long)a * H,
+          (const bf16_t*)saved[d].data_ptr() + (long)a * 3 * H,
+          (const bf16_t*)xc[d].data_ptr() + (long)a * H,
+          mask[d].p ? mask[d].p + a : nullptr,
+          (const bf16_t*)Ubwd[d].data_ptr(),
+          dsp + (long)j * 2 * ds,
+          dd + j * ddstride,
+          (bf16_t*)dpre[d].data_ptr() + (long)a * 4 * H,
           h00.data_ptr<float>() + (long)a * H,
-          Bj,
+          std::min(32, B - a),
           (long)B * H, (long)B * H, (long)B * 3 * H, (long)B * H,
           (long)B, (long)B * 4 * H};
     }
     for (int j = njobs; j < 4; ++j) jobs[j] = jobs[0];
-    const char* xpd_env = getenv("NATS_XPD");
-    const int xpd = xpd_env ? atoi(xpd_env)
-                            : (njobs == 4 ? 2 : (ngrp <= 48 ? 2 : 4));
-    hipLaunchKernelGGL(nats_gru_persistent_bwd, dim3(256), dim3(384),
-                       smem_bwd, stream, jobs[0], jobs[1], jobs[2], jobs[3],
-                       T, H, K3pad, sync_p, ngrp, njobs, xpd);
-    // final dh0 per job (dstep(0) lives in ping-pong slot 0); each job
-    // writes its chunk's rows of the (B,H) dh0 output
-    for (int j = 0; j < njobs; ++j) {
-      const int dir = j & 1;
-      const int a = (j >> 1) * 32;
-      const int Bj = std::min(32, B - a);
-      hipLaunchKernelGGL(
-          nats_gru_step_bwd_gemm, dim3(ngrp), dim3(384), 0, stream,
-          dspj + (long)j * 2 * ds,
-          (const bf16_t*)(dir == 0 ? Ubwd0 : Ubwd1).data_ptr(),
-          ddj + (long)j * 32 * H,
-          (dir == 0 ? dh0_0 : dh0_1).data_ptr<float>() + (long)a * H, Bj,
-          H, K3pad);
+    hipLaunchKernelGGL(nats_gru_persistent_bwd, dim3(NATS_PERSIST_GRID),
+                       dim3(384), plan.smem_bwd, stream, jobs[0], jobs[1],
+                       jobs[2], jobs[3], T, H, K3pad,
+                       (unsigned*)sync.data_ptr<int>(), ngrp, njobs,
+                       plan.xpd);
+  } else {
+    TORCH_CHECK(B <= 32,
+                "bidir scan: B > 32 requires the persistent path "
+                "(gru_persistent_ok)");
+    for (int t = T - 1; t >= 0; --t) {
+      // parity: step t reads dstep[(t+1)%2], writes dstep[t%2]
+      auto args = [&](int d) {
+        return GruBwdArgs{
+            dsp + (2 * d + (t + 1) % 2) * ds,
+            dd + d * ddstride,
+            dhc[d].data_ptr<float>() + (long)t * B * H,
+            (const bf16_t*)saved[d].data_ptr() + (long)t * B * 3 * H,
+            (const bf16_t*)xc[d].data_ptr() + (long)t * B * H,
+            (t == 0) ? h00.data_ptr<float>()
+                     : h_all[d].data_ptr<float>() + (long)(t - 1) * B * H,
+            mask[d].p ? mask[d].p + (long)t * B : nullptr,
+            dsp + (2 * d + t % 2) * ds,
+            dd + d * ddstride,
+            (bf16_t*)dpre[d].data_ptr() + (long)t * B * 4 * H};
+      };
+      hipLaunchKernelGGL(nats_gru_step_bwd_fused_bidir, dim3(ngrp, 2),
+                         dim3(384), 0, stream, args(0), args(1),
+                         (const bf16_t*)Ubwd[0].data_ptr(),
+                         (const bf16_t*)Ubwd[1].data_ptr(), B, H, K3pad);
     }
-    HIP_CHECK(hipGetLastError());
-    return {dpre0, dh0_0, dpre1, dh0_1};
   }
-
-  TORCH_CHECK(B <= 32,
-              "bidir scan: B > 32 requires the persistent path "
-              "(gru_persistent_ok)");
-  for (int t = T - 1; t >= 0; --t) {
-    // parity: step t reads dstep[(t+1)%2], writes dstep[t%2]
-    GruBwdArgs a0{
-        dsp + 0 * 2 * ds + ((t + 1) % 2) * ds,
-        dd + 0,
-        dh0c.data_ptr<float>() + (long)t * B * H,
-        (const bf16_t*)saved0.data_ptr() + (long)t * B * 3 * H,
-        (const bf16_t*)xc0.data_ptr() + (long)t * B * H,
-        (t == 0) ? h00.data_ptr<float>()
-                 : h_all0.data_ptr<float>() + (long)(t - 1) * B * H,
-        m0 ? m0 + (long)t * B : nullptr,
-        dsp + 0 * 2 * ds + (t % 2) * ds,
-        dd + 0,
-        (bf16_t*)dpre0.data_ptr() + (long)t * B * 4 * H};
-    GruBwdArgs a1{
-        dsp + 1 * 2 * ds + ((t + 1) % 2) * ds,
-        dd + (long)B * H,
-        dh1c.data_ptr<float>() + (long)t * B * H,
-        (const bf16_t*)saved1.data_ptr() + (long)t * B * 3 * H,
-        (const bf16_t*)xc1.data_ptr() + (long)t * B * H,
-        (t == 0) ? h00.data_ptr<float>()
-                 : h_all1.data_ptr<float>() + (long)(t - 1) * B * H,
-        m1 ? m1 + (long)t * B : nullptr,
-        dsp + 1 * 2 * ds + (t % 2) * ds,
-        dd + (long)B * H,
-        (bf16_t*)dpre1.data_ptr() + (long)t * B * 4 * H};
-    hipLaunchKernelGGL(nats_gru_step_bwd_fused_bidir, dim3(ngrp, 2),
-                       dim3(384), 0, stream, a0, a1,
-                       (const bf16_t*)Ubwd0.data_ptr(),
-                       (const bf16_t*)Ubwd1.data_ptr(), B, H, K3pad);
+  // final dh0 per job (dstep(0) lives in ping-pong slot 0); each job
+  // writes its chunk's rows of the (B,H) dh0 output
+  for (int j = 0; j < njobs; ++j) {
+    const int d = j & 1;
+    const int a = (j >> 1) * 32;
+    hipLaunchKernelGGL(nats_gru_step_bwd_gemm, dim3(ngrp), dim3(384), 0,
+                       stream, dsp + (long)j * 2 * ds,
+                       (const bf16_t*)Ubwd[d].data_ptr(), dd + j * ddstride,
+                       dh0[d].data_ptr<float>() + (long)a * H,
+                       std::min(32, B - a), H, K3pad);
   }
-  // dh0 = ddirect(0) + dstep(0) @ Ubwd^T (one plain gemm per direction)
-  hipLaunchKernelGGL(nats_gru_step_bwd_gemm, dim3(ngrp), dim3(384), 0, stream,
-                     dsp + 0 * 2 * ds + 0 * ds, (const bf16_t*)Ubwd0.data_ptr(),
-                     dd + 0, dh0_0.data_ptr<float>(), B, H, K3pad);
-  hipLaunchKernelGGL(nats_gru_step_bwd_gemm, dim3(ngrp), dim3(384), 0, stream,
-                     dsp + 1 * 2 * ds + 0 * ds, (const bf16_t*)Ubwd1.data_ptr(),
-                     dd + (long)B * H, dh0_1.data_ptr<float>(), B, H, K3pad);
   HIP_CHECK(hipGetLastError());
-  return {dpre0, dh0_0, dpre1, dh0_1};
+  return {dpre[0], dh0[0], dpre[1], dh0[1]};
 }
 
 std::vector<torch::Tensor> gru_scan_bwd(torch::Tensor dh_out,
@@ -1337,12 +1180,8 @@ std::vector<torch::Tensor> gru_scan_bwd(torch::Tensor dh_out,
   torch::Tensor hprev0 = h0.has_value()
                              ? h0->contiguous().to(torch::kFloat32)
                              : torch::zeros({B, H}, optsF);
-  const float* mask_p = nullptr;
-  torch::Tensor mask_c;
-  if (mask.has_value()) {
-    mask_c = mask->contiguous().to(torch::kFloat32);
-    mask_p = mask_c.data_ptr<float>();
-  }
+  const OptF32 mask_f(mask);
+  const float* mask_p = mask_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   const float* dh_out_p = dh_out.data_ptr<float>();
@@ -1372,21 +1211,6 @@ std::vector<torch::Tensor> gru_scan_bwd(torch::Tensor dh_out,
   return {dpre_all, dh_buf};
 }
 
-
-// Can the persistent bidirectional scans take this H (and hence batch
-// up to 64 via chunk jobs)? Mirrors the fwd/bwd gate conditions.
-bool gru_persistent_ok(long H) {
-  const long Hpad = (H + 31) / 32 * 32;
-  const long K3pad = (3 * H + 31) / 32 * 32;
-  const long ngrp = (H + JB - 1) / JB;
-  const size_t smem_fwd =
-      (size_t)3 * JB * Hpad * 2 + sizeof(float) * 3 * 32 * (JB + 1);
-  const size_t smem_bwd =
-      (size_t)JB * K3pad * 2 + sizeof(float) * 3 * 32 * (JB + 1);
-  return (2 * ngrp <= 192) && (smem_fwd <= 150 * 1024) &&
-         (smem_bwd <= 150 * 1024) &&
-         (getenv("NATS_NO_PERSISTENT") == nullptr);
-}
 
 // ---- grid-barrier micro-benchmark: isolates the per-step sync cost of
 // the persistent scans (timing evidence in profiles/README.md). ----

@@ -22,7 +22,6 @@ __global__ void fused_gradnorm_kernel(const float* const* __restrict__ gs,
                                       const int* __restrict__ chunk_tensor,
                                       const long* __restrict__ chunk_off,
                                       float* __restrict__ g2_out) {
-  __shared__ float red[BLOCK / NATS_WAVE];
   const int ci = blockIdx.x;
   const int ti = chunk_tensor[ci];
   const long off = chunk_off[ci];
@@ -36,16 +35,8 @@ __global__ void fused_gradnorm_kernel(const float* const* __restrict__ gs,
     acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
   for (long i = n4 + threadIdx.x; i < n; i += BLOCK) acc += g[i] * g[i];
-#pragma unroll
-  for (int o = NATS_WAVE / 2; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-  if ((threadIdx.x & (NATS_WAVE - 1)) == 0)
-    red[threadIdx.x / NATS_WAVE] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int w = 0; w < BLOCK / NATS_WAVE; ++w) s += red[w];
-    atomicAdd(g2_out, s);
-  }
+  const float s = block_reduce_sum(acc);
+  if (threadIdx.x == 0) atomicAdd(g2_out, s);
 }
 
 // clip scale computed on-device (no host sync): scale = clip_c/sqrt(g2)

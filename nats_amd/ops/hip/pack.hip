@@ -14,8 +14,6 @@
 
 namespace {
 
-constexpr int JB = 16;
-
 // forward scan operand: [ngrp*3*16][Hpad]; group g of row-block grp holds
 // output columns j=grp*16+c of (g0: U[:, :H], g1: U[:, H:], g2: Ux)
 // transposed; zero outside.
@@ -121,8 +119,6 @@ __global__ void pack_gru1_kernel(const float* __restrict__ U_1,  // [H][2H]
   }
 }
 
-inline int cdiv_p(int a, int b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 torch::Tensor pack_fwd_weights_hip(torch::Tensor U, torch::Tensor Ux) {
@@ -130,13 +126,13 @@ torch::Tensor pack_fwd_weights_hip(torch::Tensor U, torch::Tensor Ux) {
   auto Uc = U.contiguous();
   auto Uxc = Ux.contiguous();
   const int H = Ux.size(1);
-  const int ngrp = cdiv_p(H, JB);
-  const int Hpad = cdiv_p(H, 32) * 32;
+  const int ngrp = cdiv(H, JB);
+  const int Hpad = cdiv(H, 32) * 32;
   const int nrows = ngrp * 3 * JB;
   auto out = torch::empty({nrows, Hpad},
                           U.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  hipLaunchKernelGGL(pack_fwd_kernel, dim3(cdiv_p(nrows, 4)), dim3(256), 0,
+  hipLaunchKernelGGL(pack_fwd_kernel, dim3(cdiv(nrows, 4)), dim3(256), 0,
                      stream, Uc.data_ptr<float>(), Uxc.data_ptr<float>(),
                      (bf16_t*)out.data_ptr(), H, Hpad, nrows);
   HIP_CHECK(hipGetLastError());
@@ -151,7 +147,7 @@ torch::Tensor pack_cat2_hip(torch::Tensor A, torch::Tensor B, long R,
   const int rows0 = A.size(0);
   auto out = torch::empty({R, K}, A.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  hipLaunchKernelGGL(pack_cat2_kernel, dim3(cdiv_p((int)R, 4)), dim3(256), 0,
+  hipLaunchKernelGGL(pack_cat2_kernel, dim3(cdiv((int)R, 4)), dim3(256), 0,
                      stream, Ac.data_ptr<float>(), Bc.data_ptr<float>(),
                      (bf16_t*)out.data_ptr(), rows0, (int)A.size(1),
                      (int)B.size(1), (int)R, (int)K);
@@ -167,7 +163,7 @@ torch::Tensor pack_pad_hip(torch::Tensor src, long R, long K,
   const int cols0 = transpose ? src.size(0) : src.size(1);
   auto out = torch::empty({R, K}, src.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  hipLaunchKernelGGL(pack_pad_kernel, dim3(cdiv_p((int)R, 4)), dim3(256), 0,
+  hipLaunchKernelGGL(pack_pad_kernel, dim3(cdiv((int)R, 4)), dim3(256), 0,
                      stream, Sc.data_ptr<float>(), (bf16_t*)out.data_ptr(),
                      rows0, cols0, (int)R, (int)K, transpose ? 1 : 0);
   HIP_CHECK(hipGetLastError());
@@ -184,12 +180,12 @@ torch::Tensor pack_gru1_weights_hip(torch::Tensor U_1, torch::Tensor W_1,
   auto d = Wx_1.contiguous();
   const int H = Ux_1.size(0);
   const int C = W_1.size(0);
-  const int ngrp = cdiv_p(H, JB);
+  const int ngrp = cdiv(H, JB);
   const int nrows = ngrp * 4 * JB;
   auto out = torch::empty({nrows, Hpad + Cpad},
                           U_1.options().dtype(torch::kBFloat16));
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  hipLaunchKernelGGL(pack_gru1_kernel, dim3(cdiv_p(nrows, 4)), dim3(256), 0,
+  hipLaunchKernelGGL(pack_gru1_kernel, dim3(cdiv(nrows, 4)), dim3(256), 0,
                      stream, a.data_ptr<float>(), b.data_ptr<float>(),
                      c.data_ptr<float>(), d.data_ptr<float>(),
                      (bf16_t*)out.data_ptr(), H, C, (int)Hpad, (int)Cpad,

@@ -55,23 +55,19 @@ def _use_hip(*tensors):
     return True
 
 
-def gru_scan(x_gates, x_cand, mask, U, Ux, h0=None):
-    """GRU scan over time. Returns hidden states (T, B, H).
+def weights_version(params):
+    """Monotone tag over ``params``, the key of every cache derived from
+    weights (packed decoder operands, captured decode graphs): in-place
+    torch updates bump tensor _version; updates through raw pointers (the
+    fused adadelta kernel, graph replays) never do, so their callers
+    advance an explicit epoch with ``bump_update_epoch``."""
+    return tuple((p._version, getattr(p, "_nats_update_epoch", 0))
+                 for p in params)
 
-    Semantics: nats.py:336-372 (gru_layer step). ``x_gates``/``x_cand`` are
-    the hoisted input projections x@W+b (T,B,2H) and x@Wx+bx (T,B,H).
-    """
-    if _use_hip(x_gates, U):
-        from .gru import gru_scan_hip
-        B = x_gates.shape[1]
-        if B <= MAX_KERNEL_BATCH:
-            return gru_scan_hip(x_gates, x_cand, mask, U, Ux, h0)
-        return torch.cat([gru_scan_hip(
-            x_gates[:, a:b], x_cand[:, a:b],
-            mask[:, a:b] if mask is not None else None, U, Ux,
-            h0[a:b] if h0 is not None else None)
-            for a, b in _batch_chunks(B)], dim=1)
-    return eager.gru_scan(x_gates, x_cand, mask, U, Ux, h0)
+
+def bump_update_epoch(params):
+    for p in params:
+        p._nats_update_epoch = getattr(p, "_nats_update_epoch", 0) + 1
 
 
 MAX_KERNEL_BATCH = 32  # MFMA M-tiling of the step kernels (2x 16-row tiles)
@@ -94,32 +90,75 @@ def _chunk_streams(device, n):
     return pool[:n]
 
 
+def _opt_slice(t, a, b, dim):
+    return None if t is None else t.narrow(dim, a, b - a)
+
+
+def _run_chunks(call, B, cat_dims, concurrent):
+    """Batches beyond the kernels' 32-row MFMA tiling run as exact per-chunk
+    passes (batch rows are independent): ``call(a, b)`` returns the tuple of
+    outputs for rows [a, b); output i is concatenated along ``cat_dims[i]``.
+
+    ``concurrent`` runs the chunks as chains on separate HIP streams: the
+    per-step decoder kernels occupy a fraction of the chip each, and the
+    chains are independent (autograd replays each backward on its recorded
+    stream, so the reverse chains overlap too; for beam batches it doubles
+    the serving micro-batch row budget)."""
+    chunks = _batch_chunks(B)
+    if concurrent:
+        cur = torch.cuda.current_stream()
+        streams = _chunk_streams(cur.device, len(chunks))
+        outs = []
+        for (a, b), s in zip(chunks, streams):
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                outs.append(call(a, b))
+        for s in streams:
+            cur.wait_stream(s)
+        for o in outs:
+            for t in o:
+                t.record_stream(cur)
+    else:
+        outs = [call(a, b) for a, b in chunks]
+    return tuple(torch.cat([o[i] for o in outs], dim=d)
+                 for i, d in enumerate(cat_dims))
+
+
+def gru_scan(x_gates, x_cand, mask, U, Ux, h0=None):
+    """GRU scan over time. Returns hidden states (T, B, H).
+
+    Semantics: nats.py:336-372 (gru_layer step). ``x_gates``/``x_cand`` are
+    the hoisted input projections x@W+b (T,B,2H) and x@Wx+bx (T,B,H).
+    """
+    if _use_hip(x_gates, U):
+        from .gru import gru_scan_hip
+        B = x_gates.shape[1]
+        if B <= MAX_KERNEL_BATCH:
+            return gru_scan_hip(x_gates, x_cand, mask, U, Ux, h0)
+        return _run_chunks(lambda a, b: (gru_scan_hip(
+            x_gates[:, a:b], x_cand[:, a:b], _opt_slice(mask, a, b, 1), U, Ux,
+            _opt_slice(h0, a, b, 0)),), B, (1,), concurrent=False)[0]
+    return eager.gru_scan(x_gates, x_cand, mask, U, Ux, h0)
+
+
 def gru_scan_bidir(xg0, xc0, mask0, U0, Ux0, xg1, xc1, mask1, U1, Ux1):
     """Both encoder directions (independent scans) in one fused launch
-    sequence on GPU; two eager scans on CPU. Returns (h_fwd, h_bwd).
-
-    Batches beyond the kernels' 32-row MFMA tiling are processed in exact
-    per-chunk passes (batch rows are independent)."""
+    sequence on GPU; two eager scans on CPU. Returns (h_fwd, h_bwd)."""
     if _use_hip(xg0, U0):
         from .gru import gru_scan_bidir_hip
         B = xg0.shape[1]
         # the persistent scans take up to 64 rows natively (two 32-row
         # chunk jobs concurrent in one launch — same barrier count as 32)
         direct_max = MAX_KERNEL_BATCH
-        if _hip_ext() is not None and _hip_ext().gru_persistent_ok(
-                U0.shape[0], 2 * MAX_KERNEL_BATCH):
+        if _hip_ext().gru_persistent_ok(U0.shape[0], 2 * MAX_KERNEL_BATCH):
             direct_max = 2 * MAX_KERNEL_BATCH
         if B <= direct_max:
             return gru_scan_bidir_hip(xg0, xc0, mask0, U0, Ux0, xg1, xc1,
                                       mask1, U1, Ux1)
-        outs = [gru_scan_bidir_hip(
-            xg0[:, a:b], xc0[:, a:b],
-            mask0[:, a:b] if mask0 is not None else None, U0, Ux0,
-            xg1[:, a:b], xc1[:, a:b],
-            mask1[:, a:b] if mask1 is not None else None, U1, Ux1)
-            for a, b in _batch_chunks(B)]
-        return (torch.cat([o[0] for o in outs], dim=1),
-                torch.cat([o[1] for o in outs], dim=1))
+        return _run_chunks(lambda a, b: gru_scan_bidir_hip(
+            xg0[:, a:b], xc0[:, a:b], _opt_slice(mask0, a, b, 1), U0, Ux0,
+            xg1[:, a:b], xc1[:, a:b], _opt_slice(mask1, a, b, 1), U1, Ux1),
+            B, (1, 1), concurrent=False)
     return (eager.gru_scan(xg0, xc0, mask0, U0, Ux0),
             eager.gru_scan(xg1, xc1, mask1, U1, Ux1))
 
@@ -136,31 +175,10 @@ def cond_gru_scan(y_gates, y_cand, mask, init_state, ctx, ctx_mask, pctx, P):
         if B <= MAX_KERNEL_BATCH:
             return cond_gru_scan_hip(y_gates, y_cand, mask, init_state, ctx,
                                      ctx_mask, pctx, P)
-        # batches beyond the 32-row MFMA tiling run as CONCURRENT chunk
-        # chains on separate HIP streams: the per-step decoder kernels
-        # occupy a fraction of the chip each, and the chains are
-        # independent (autograd replays each backward on its recorded
-        # stream, so the reverse chains overlap too)
-        chunks = _batch_chunks(B)
-        cur = torch.cuda.current_stream()
-        streams = _chunk_streams(y_gates.device, len(chunks))
-        outs = []
-        for (a, b), s in zip(chunks, streams):
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                outs.append(cond_gru_scan_hip(
-                    y_gates[:, a:b], y_cand[:, a:b],
-                    mask[:, a:b] if mask is not None else None,
-                    init_state[a:b], ctx[:, a:b],
-                    ctx_mask[:, a:b] if ctx_mask is not None else None,
-                    pctx[:, a:b], P))
-        for s in streams:
-            cur.wait_stream(s)
-        for o in outs:
-            for t in o:
-                t.record_stream(cur)
-        return tuple(torch.cat([o[i] for o in outs],
-                               dim=1 if i < 3 else 0) for i in range(5))
+        return _run_chunks(lambda a, b: cond_gru_scan_hip(
+            y_gates[:, a:b], y_cand[:, a:b], _opt_slice(mask, a, b, 1),
+            init_state[a:b], ctx[:, a:b], _opt_slice(ctx_mask, a, b, 1),
+            pctx[:, a:b], P), B, (1, 1, 1, 0, 0), concurrent=True)
     return eager.cond_gru_scan(y_gates, y_cand, mask, init_state, ctx,
                                ctx_mask, pctx, P)
 
@@ -176,26 +194,10 @@ def cond_gru_step(h_prev, x_g, x_c, ctx, ctx_mask, pctx, acc_ctx, acc_alpha, P):
         if B <= MAX_KERNEL_BATCH:
             return cond_gru_step_hip(h_prev, x_g, x_c, ctx, ctx_mask, pctx,
                                      acc_ctx, acc_alpha, P)
-        # beam batches beyond the 32-row tiling: concurrent chunk chains
-        # on side streams (doubles the serving micro-batch row budget)
-        chunks = _batch_chunks(B)
-        cur = torch.cuda.current_stream()
-        streams = _chunk_streams(h_prev.device, len(chunks))
-        outs = []
-        for (a, b), s in zip(chunks, streams):
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                outs.append(cond_gru_step_hip(
-                    h_prev[a:b], x_g[a:b], x_c[a:b], ctx[:, a:b],
-                    ctx_mask[:, a:b] if ctx_mask is not None else None,
-                    pctx[:, a:b], acc_ctx[a:b], acc_alpha[a:b], P))
-        for s in streams:
-            cur.wait_stream(s)
-        for o in outs:
-            for t in o:
-                t.record_stream(cur)
-        return tuple(torch.cat([o[i] for o in outs], dim=0)
-                     for i in range(5))
+        return _run_chunks(lambda a, b: cond_gru_step_hip(
+            h_prev[a:b], x_g[a:b], x_c[a:b], ctx[:, a:b],
+            _opt_slice(ctx_mask, a, b, 1), pctx[:, a:b], acc_ctx[a:b],
+            acc_alpha[a:b], P), B, (0,) * 5, concurrent=True)
     return eager.cond_gru_step(h_prev, x_g, x_c, ctx, ctx_mask, pctx,
                                acc_ctx, acc_alpha, P)
 

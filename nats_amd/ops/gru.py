@@ -16,8 +16,21 @@ from . import _hip_ext
 JB = 16
 
 
+def _ceil(x, m):
+    return (x + m - 1) // m * m
+
+
 def _pad_to(x, rows, cols):
     return F.pad(x, (0, cols - x.shape[1], 0, rows - x.shape[0]))
+
+
+def _save_opt(t):
+    """save_for_backward takes no None: an absent tensor is saved empty."""
+    return t if t is not None else torch.empty(0)
+
+
+def _load_opt(t):
+    return t if t.numel() else None
 
 
 def pack_fwd_weights(U, Ux):
@@ -31,9 +44,9 @@ def pack_fwd_weights(U, Ux):
         if ext is not None:
             return ext.pack_fwd_weights(U, Ux)
     H = Ux.shape[1]
-    ngrp = (H + JB - 1) // JB
-    rows = ngrp * JB
-    Hpad = ((H + 31) // 32) * 32
+    rows = _ceil(H, JB)
+    ngrp = rows // JB
+    Hpad = _ceil(H, 32)
     Ut = _pad_to(U[:, :H].t(), rows, Hpad)
     Uu = _pad_to(U[:, H:].t(), rows, Hpad)
     Uxt = _pad_to(Ux.t(), rows, Hpad)
@@ -45,16 +58,30 @@ def pack_fwd_weights(U, Ux):
 def pack_bwd_weights(U, Ux):
     """[ngrp*16, K3pad] bf16: row i = [U[i, :2H] | Ux[i, :]] zero-padded."""
     H = Ux.shape[1]
-    ngrp = (H + JB - 1) // JB
-    rows = ngrp * JB
-    K3 = 3 * H
-    K3pad = ((K3 + 31) // 32) * 32
+    rows = _ceil(H, JB)
+    K3pad = _ceil(3 * H, 32)
     if U.is_cuda and U.dtype == torch.float32:
         ext = _hip_ext()
         if ext is not None:
             return ext.pack_cat2(U, Ux, rows, K3pad)
     cat = torch.cat([U, Ux], dim=1)                   # (H, 3H)
     return _pad_to(cat, rows, K3pad).to(torch.bfloat16).contiguous()
+
+
+def gru_weight_grads(h_all, dpre_all, h0=None):
+    """Time-batched weight grads of one GRU scan from its hidden states
+    (T,B,H) and stored preactivation grads (T,B,4H): dU = hprev^T @
+    [dpr|dpu], dUx = hprev^T @ dpxl (one GEMM each over all T*B positions),
+    where hprev is h_all shifted one step with ``h0`` (zeros if None) in
+    front. Returns (dU, dUx) in fp32."""
+    T, B, H = h_all.shape
+    first = (torch.zeros_like(h_all[:1]) if h0 is None
+             else h0.float().unsqueeze(0))
+    flat_h = torch.cat([first, h_all[:-1]], dim=0).reshape(
+        T * B, H).to(torch.bfloat16)
+    dU = (flat_h.t() @ dpre_all[..., :2 * H].reshape(T * B, 2 * H)).float()
+    dUx = (flat_h.t() @ dpre_all[..., 3 * H:].reshape(T * B, H)).float()
+    return dU, dUx
 
 
 class GRUScanFn(torch.autograd.Function):
@@ -66,9 +93,8 @@ class GRUScanFn(torch.autograd.Function):
         xc = xc.to(torch.bfloat16).contiguous()
         Upk = pack_fwd_weights(U, Ux)
         h_all, saved = ext.gru_scan_fwd(xg, xc, mask, Upk, h0)
-        ctx.save_for_backward(xc, h_all, saved, U, Ux,
-                              mask if mask is not None else torch.empty(0),
-                              h0 if h0 is not None else torch.empty(0))
+        ctx.save_for_backward(xc, h_all, saved, U, Ux, _save_opt(mask),
+                              _save_opt(h0))
         ctx.xg_dtype = xg_dtype
         return h_all
 
@@ -76,24 +102,14 @@ class GRUScanFn(torch.autograd.Function):
     def backward(ctx, dh_out):
         ext = _hip_ext()
         xc, h_all, saved, U, Ux, mask, h0 = ctx.saved_tensors
-        mask = mask if mask.numel() else None
-        h0v = h0 if h0.numel() else None
-        T, B, H = h_all.shape
+        mask, h0 = _load_opt(mask), _load_opt(h0)
+        H = h_all.shape[2]
         Ubwd = pack_bwd_weights(U, Ux)
         dpre_all, dh0 = ext.gru_scan_bwd(
-            dh_out.contiguous().float(), h_all, saved, xc, mask, Ubwd, h0v)
+            dh_out.contiguous().float(), h_all, saved, xc, mask, Ubwd, h0)
         dxg = dpre_all[..., :2 * H]
         dxc = dpre_all[..., 2 * H:3 * H]
-        # time-batched weight grads: dU = hprev^T @ [dpr|dpu],
-        # dUx = hprev^T @ dpxl (one GEMM each over all T*B positions)
-        if h0v is not None:
-            h_prev = torch.cat([h0v.unsqueeze(0).float(), h_all[:-1]], dim=0)
-        else:
-            h_prev = torch.cat([torch.zeros_like(h_all[:1]), h_all[:-1]],
-                               dim=0)
-        flat_h = h_prev.reshape(T * B, H).to(torch.bfloat16)
-        dU = (flat_h.t() @ dpre_all[..., :2 * H].reshape(T * B, 2 * H)).float()
-        dUx = (flat_h.t() @ dpre_all[..., 3 * H:].reshape(T * B, H)).float()
+        dU, dUx = gru_weight_grads(h_all, dpre_all, h0)
         need_h0 = ctx.needs_input_grad[5]
         return (dxg.to(ctx.xg_dtype), dxc.to(ctx.xg_dtype), None,
                 dU.to(U.dtype), dUx.to(Ux.dtype),
@@ -120,11 +136,8 @@ class BidirGRUScanFn(torch.autograd.Function):
         h_all0, saved0, h_all1, saved1 = ext.gru_scan_fwd_bidir(
             xg0, xc0, mask0, pack_fwd_weights(U0, Ux0),
             xg1, xc1, mask1, pack_fwd_weights(U1, Ux1))
-        e = torch.empty(0)
-        ctx.save_for_backward(xc0, h_all0, saved0, U0, Ux0,
-                              mask0 if mask0 is not None else e,
-                              xc1, h_all1, saved1, U1, Ux1,
-                              mask1 if mask1 is not None else e)
+        ctx.save_for_backward(xc0, h_all0, saved0, U0, Ux0, _save_opt(mask0),
+                              xc1, h_all1, saved1, U1, Ux1, _save_opt(mask1))
         return h_all0, h_all1
 
     @staticmethod
@@ -132,24 +145,14 @@ class BidirGRUScanFn(torch.autograd.Function):
         ext = _hip_ext()
         (xc0, h_all0, saved0, U0, Ux0, mask0,
          xc1, h_all1, saved1, U1, Ux1, mask1) = ctx.saved_tensors
-        mask0 = mask0 if mask0.numel() else None
-        mask1 = mask1 if mask1.numel() else None
-        T, B, H = h_all0.shape
+        H = h_all0.shape[2]
         dpre0, dh00, dpre1, dh01 = ext.gru_scan_bwd_bidir(
-            dh0_out.contiguous().float(), h_all0, saved0, xc0, mask0,
-            pack_bwd_weights(U0, Ux0),
-            dh1_out.contiguous().float(), h_all1, saved1, xc1, mask1,
-            pack_bwd_weights(U1, Ux1))
-
-        def wgrads(h_all, dpre):
-            h_prev = torch.cat([torch.zeros_like(h_all[:1]), h_all[:-1]], 0)
-            fh = h_prev.reshape(T * B, H).to(torch.bfloat16)
-            dU = (fh.t() @ dpre[..., :2 * H].reshape(T * B, 2 * H)).float()
-            dUx = (fh.t() @ dpre[..., 3 * H:].reshape(T * B, H)).float()
-            return dU, dUx
-
-        dU0, dUx0 = wgrads(h_all0, dpre0)
-        dU1, dUx1 = wgrads(h_all1, dpre1)
+            dh0_out.contiguous().float(), h_all0, saved0, xc0,
+            _load_opt(mask0), pack_bwd_weights(U0, Ux0),
+            dh1_out.contiguous().float(), h_all1, saved1, xc1,
+            _load_opt(mask1), pack_bwd_weights(U1, Ux1))
+        dU0, dUx0 = gru_weight_grads(h_all0, dpre0)
+        dU1, dUx1 = gru_weight_grads(h_all1, dpre1)
         xt = ctx.xg_dtype
         pt = U0.dtype
         return (dpre0[..., :2 * H].to(xt), dpre0[..., 2 * H:3 * H].to(xt),

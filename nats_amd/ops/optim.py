@@ -7,7 +7,7 @@ engine.optim.Adadelta + clip_grads_global_norm (nats.py:1145-1173,
 import torch
 
 from ..engine.optim import Adadelta
-from . import _hip_ext
+from . import _hip_ext, bump_update_epoch
 
 CHUNK = 1 << 16
 
@@ -67,10 +67,5 @@ class FusedAdadelta(Adadelta):
         # packed-weight cache (ops/cond_gru.py _step_packed) and the
         # hipGraph stepper cache (decode/graph.py). Bump an explicit
         # update epoch on each parameter so those caches see the change.
-        for p in ps:
-            p._nats_update_epoch = getattr(p, "_nats_update_epoch", 0) + 1
+        bump_update_epoch(ps)
         return torch.sqrt(g2[0])  # pre-clip norm, no host sync
-
-    @torch.no_grad()
-    def _update(self):  # pragma: no cover - only used via super().step()
-        Adadelta._update(self)

@@ -22,6 +22,8 @@ backend) raise at capture time and disable graphing for the session.
 
 import torch
 
+from ..ops import bump_update_epoch
+
 
 class GraphedTrainStep:
     """Replayable fwd+bwd+optimizer step for one input shape."""
@@ -103,8 +105,7 @@ class GraphedTrainStep:
         # replays run the fused optimizer kernel without re-entering
         # python, so bump the update epoch the decode/pack caches key on
         # (ops/optim.py does this on the eager path)
-        for p in self.model.parameters():
-            p._nats_update_epoch = getattr(p, "_nats_update_epoch", 0) + 1
+        bump_update_epoch(self.model.parameters())
         return self.cost
 
 

@@ -781,3 +781,46 @@ def test_gru_scan_bidir_large_batch(ext, B):
                           ["xg0", "xc0", "U0", "Ux0", "xg1", "xc1", "U1",
                            "Ux1"]):
         assert_grad_close(r.grad, h.grad.cpu().float(), name, rel=0.08)
+
+
+def test_cond_gru_one_step_large_batch(ext):
+    """B > 32 through the op layer: chunks of 32 + 8 rows on side streams,
+    with per-column context lengths and per-row accumulators, so a chunk
+    sliced along the wrong dim cannot pass."""
+    from nats_amd import ops
+    from nats_amd.ops import eager
+    B, Ts = 40, 6
+    model, yg, yc, _, init, ctx, _ = _cond_inputs(T=1, B=B, H=16, Ts=Ts, A=8,
+                                                  with_masks=False)
+    g = torch.Generator().manual_seed(9)
+    slens = torch.randint(2, Ts + 1, (B,), generator=g)
+    assert all(len(set(c.tolist())) > 1 for c in (slens[:32], slens[32:]))
+    ctx_mask = (torch.arange(Ts).unsqueeze(1) < slens.unsqueeze(0)).float()
+    P = {k: v.detach() for k, v in model.P.items()}
+    pctx = ctx @ P["decoder_Wc_att"] + P["decoder_b_att"]
+    acc_c = torch.randn(B, ctx.shape[2], generator=g) * 0.1
+    acc_a = torch.rand(B, Ts, generator=g)
+    ref = eager.cond_gru_step(init, yg[0], yc[0], ctx, ctx_mask, pctx,
+                              acc_c, acc_a, P)
+    Pg = {k: v.cuda() for k, v in P.items()}
+    out = ops.cond_gru_step(init.cuda(), yg[0].cuda(), yc[0].cuda(),
+                            ctx.cuda(), ctx_mask.cuda(), pctx.cuda(),
+                            acc_c.cuda(), acc_a.cuda(), Pg)
+    for r, o in zip(ref, out):
+        assert o.shape == r.shape
+        torch.testing.assert_close(o.cpu(), r, rtol=5e-2, atol=5e-2)
+    alpha = out[2].cpu()
+    assert alpha.shape == (B, Ts)
+    assert bool((alpha[ctx_mask.t() == 0] == 0).all())
+
+
+def test_gru_scan_large_batch(ext):
+    """B > 32 through the op layer: serial chunks of 32 + 8 rows."""
+    from nats_amd import ops
+    from nats_amd.ops import eager
+    xg, xc, U, Ux, mask = _gru_inputs(T=7, B=40, H=16)
+    ref = eager.gru_scan(xg, xc, mask, U, Ux)
+    out = ops.gru_scan(xg.cuda(), xc.cuda(), mask.cuda(), U.cuda(),
+                       Ux.cuda())
+    assert out.shape == ref.shape
+    torch.testing.assert_close(out.cpu(), ref, rtol=0.1, atol=6e-2)

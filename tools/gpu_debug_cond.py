@@ -11,9 +11,7 @@ import torch
 
 from nats_amd.models.distraction import NatsModel, default_options
 from nats_amd.ops import eager
-from nats_amd.ops.cond_gru import (_ceil, _pack_rows, pack_gru1_weights,
-                                   CondGRUScanFn)
-from nats_amd.ops.gru import pack_fwd_weights
+from nats_amd.ops.cond_gru import DECODER_KEYS, pack_decoder_fwd
 from nats_amd.ops import _hip_ext
 
 
@@ -61,21 +59,11 @@ def main():
     # HIP
     dev = "cuda"
     Pg = {k: v.to(dev) for k, v in P.items()}
-    Hpad, Cpad = _ceil(H, 32), _ceil(C, 32)
-    Upk2 = pack_fwd_weights(Pg["decoder_U"], Pg["decoder_Ux"])
-    W1pk = pack_gru1_weights(Pg["decoder_U_1"], Pg["decoder_W_1"],
-                             Pg["decoder_Ux_1"], Pg["decoder_Wx_1"], Hpad,
-                             Cpad)
-    WattPk = _pack_rows(Pg["decoder_W_att"].t(), _ceil(A, 16), Hpad)
     outs = ext.cond_gru_fwd(
         yg.to(dev).to(torch.bfloat16), yc.to(dev).to(torch.bfloat16), None,
         init.to(dev), ctx.to(dev).to(torch.bfloat16), None,
-        pctx.to(dev).float().contiguous(), Upk2, W1pk, WattPk,
-        Pg["decoder_b_1"].contiguous(), Pg["decoder_bx_1"].contiguous(),
-        Pg["decoder_U_att"].reshape(-1).contiguous(), 0.0,
-        Pg["decoder_D_wei"].reshape(-1).contiguous(),
-        Pg["decoder_W_con"].reshape(-1).contiguous(),
-        Pg["decoder_U_con"].reshape(-1).contiguous(), None, None)
+        pctx.to(dev).float().contiguous(),
+        *pack_decoder_fwd(*[Pg[k] for k in DECODER_KEYS]), None, None)
     (h2_all, ctxs_all, alphas_all, accC, accA, h1_all, saved2, saved1,
      pstate_all, ctxpre_all, accA_used, accC_used) = outs
 

@@ -142,7 +142,9 @@ def softmax_xent(logits, targets):
     """Per-position negative log-likelihood (nats.py:763-768).
 
     logits (N,V), targets (N,) -> (N,) in logits.dtype's accumulation
-    precision (fp32).
+    precision (fp32; fp64 logits stay fp64, for use as a test oracle).
     """
-    logp = torch.log_softmax(logits.float(), dim=-1)
+    if logits.dtype != torch.float64:
+        logits = logits.float()
+    logp = torch.log_softmax(logits, dim=-1)
     return -logp.gather(1, targets.unsqueeze(1)).squeeze(1)

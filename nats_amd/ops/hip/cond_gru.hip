@@ -260,7 +260,7 @@ __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
     float* __restrict__ h2_t,          // [B][H] out
     bf16_t* __restrict__ h2bf_out,     // [32][Hpad] out
     int ld_h2bf,
-    bf16_t* __restrict__ saved1_t,     // [B][4H] (r2,u2,pxa,hbar)
+    float* __restrict__ saved1_t,      // [B][4H] (r2,u2,pxa,hbar)
     int B, int H, int K1) {
   __shared__ float pre[4][2][32][JB + 1];
 
@@ -293,10 +293,10 @@ __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
         h1_t[(long)b * H + j], mask_t, b);
     h2_t[(long)b * H + j] = o.hnew;
     h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
-    saved1_t[(long)b * 4 * H + j] = (bf16_t)o.r;
-    saved1_t[(long)b * 4 * H + H + j] = (bf16_t)o.u;
-    saved1_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)pxa;
-    saved1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.hbar;
+    saved1_t[(long)b * 4 * H + j] = o.r;
+    saved1_t[(long)b * 4 * H + H + j] = o.u;
+    saved1_t[(long)b * 4 * H + 2 * H + j] = pxa;
+    saved1_t[(long)b * 4 * H + 3 * H + j] = o.hbar;
   }
 }
 
@@ -354,7 +354,7 @@ __global__ void cond_gru1_step_pointwise(
     float* __restrict__ h2_t,          // [B][H] out
     bf16_t* __restrict__ h2bf_out,     // [32][ld_h2bf] out
     int ld_h2bf,
-    bf16_t* __restrict__ saved1_t,     // [B][4H] (r2,u2,pxa,hbar)
+    float* __restrict__ saved1_t,      // [B][4H] (r2,u2,pxa,hbar)
     int B, int H, int Hpad) {
   const long total = (long)B * H;
   for (long idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -375,10 +375,10 @@ __global__ void cond_gru1_step_pointwise(
                                       pxa + bx1[j], p3, h1_t[idx], mask_t, b);
     h2_t[idx] = o.hnew;
     h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
-    saved1_t[(long)b * 4 * H + j] = (bf16_t)o.r;
-    saved1_t[(long)b * 4 * H + H + j] = (bf16_t)o.u;
-    saved1_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)pxa;
-    saved1_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.hbar;
+    saved1_t[(long)b * 4 * H + j] = o.r;
+    saved1_t[(long)b * 4 * H + H + j] = o.u;
+    saved1_t[(long)b * 4 * H + 2 * H + j] = pxa;
+    saved1_t[(long)b * 4 * H + 3 * H + j] = o.hbar;
   }
 }
 
@@ -393,7 +393,7 @@ __global__ void cond_gru1_bwd_pointwise(
     const float* __restrict__ dh_carry,   // [B][H] (split-K half 0)
     const float* __restrict__ dh_carry2,  // [B][H] half 1 or null
     const float* __restrict__ dh2_all_t,  // [B][H] or null
-    const bf16_t* __restrict__ saved1_t,  // [B][4H]
+    const float* __restrict__ saved1_t,   // [B][4H]
     const float* __restrict__ h1_all_t,   // [B][H]
     const float* __restrict__ bx1,        // [H]
     const float* __restrict__ mask_t,     // [B] or null
@@ -431,10 +431,10 @@ __global__ void cond_gru1_bwd_pointwise(
     float dh2 = dh_carry[idx];
     if (dh_carry2 != nullptr) dh2 += dh_carry2[idx];
     if (dh2_all_t != nullptr) dh2 += dh2_all_t[idx];
-    const float r2 = (float)saved1_t[(long)b * 4 * H + j];
-    const float u2 = (float)saved1_t[(long)b * 4 * H + H + j];
-    const float pxa = (float)saved1_t[(long)b * 4 * H + 2 * H + j];
-    const float hbar = (float)saved1_t[(long)b * 4 * H + 3 * H + j];
+    const float r2 = saved1_t[(long)b * 4 * H + j];
+    const float u2 = saved1_t[(long)b * 4 * H + H + j];
+    const float pxa = saved1_t[(long)b * 4 * H + 2 * H + j];
+    const float hbar = saved1_t[(long)b * 4 * H + 3 * H + j];
     const float h1v = h1_all_t[idx];
     const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
     const GruCellBwd o =
@@ -688,7 +688,8 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_dot(
 
 // attention backward, stage 2 (grid (B, ceil(Ts/256))): softmax backward,
 // per-(s,i) dpc into dpctx_acc + acc_alpha carry; tanh values stored to
-// pc_buf [B][A][Ts] (coalesced in s) for the stage-3 reduction.
+// pc_buf [B][A][Ts] (coalesced in s) for the stage-3 reduction, in fp32:
+// the reduction forms 1 - pc^2, which a bf16 copy of a saturated pc loses.
 __global__ __launch_bounds__(256) void cond_attn_bwd_scatter(
     const float* __restrict__ alphas_t,     // [B][Ts]
     const float* __restrict__ dal_buf,      // [Ts][B]
@@ -699,7 +700,7 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_scatter(
     const float* __restrict__ Dwei, const float* __restrict__ Uatt,
     float* __restrict__ daccA,              // [B][Ts] (+=, atomic)
     float* __restrict__ dpctx_acc,          // [Ts][B][A] (+=)
-    bf16_t* __restrict__ pc_buf,            // [B][A][Tpad8]
+    float* __restrict__ pc_buf,             // [B][A][Tpad8]
     int B, int Ts, int A, int Tpad8) {
   // grid (B, s-chunks, A-chunks): the un-chunked variant ran only
   // B * Ts/256 blocks (2 waves/CU at the CNN/DM shape) and was
@@ -741,17 +742,17 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_scatter(
     dpv.w += d3;
     *(float4*)(dprow + i) = dpv;
     daccA_add += d0 * dw.x + d1 * dw.y + d2 * dw.z + d3 * dw.w;
-    pc_buf[((long)b * A + i) * Tpad8 + s] = (bf16_t)pc0;
-    pc_buf[((long)b * A + i + 1) * Tpad8 + s] = (bf16_t)pc1;
-    pc_buf[((long)b * A + i + 2) * Tpad8 + s] = (bf16_t)pc2;
-    pc_buf[((long)b * A + i + 3) * Tpad8 + s] = (bf16_t)pc3;
+    pc_buf[((long)b * A + i) * Tpad8 + s] = pc0;
+    pc_buf[((long)b * A + i + 1) * Tpad8 + s] = pc1;
+    pc_buf[((long)b * A + i + 2) * Tpad8 + s] = pc2;
+    pc_buf[((long)b * A + i + 3) * Tpad8 + s] = pc3;
   }
   for (; i < iend; ++i) {
     const float pc = tanhf(prow[i] + srow[i] + accAu * Dwei[i]);
     const float dpc = de * (1.f - pc * pc) * Uatt[i];
     dprow[i] += dpc;
     daccA_add += dpc * Dwei[i];
-    pc_buf[((long)b * A + i) * Tpad8 + s] = (bf16_t)pc;
+    pc_buf[((long)b * A + i) * Tpad8 + s] = pc;
   }
   if (ACH == 1) {
     daccA[(long)b * Ts + s] += daccA_add;
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
     const float* __restrict__ dal_buf,      // [Ts][B]
     const float* __restrict__ dot_buf,      // [B]
     const float* __restrict__ accA_used_t,  // [B][Ts]
-    const bf16_t* __restrict__ pc_buf,      // [B][A][Tpad8]
+    const float* __restrict__ pc_buf,       // [B][A][Tpad8]
     const float* __restrict__ Uatt,
     float* __restrict__ dpstate_t,          // [B][A]
     float* __restrict__ gdDwei,             // [A] (atomic)
@@ -794,14 +795,14 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
   const float dc_blk = block_reduce_sum(dc);  // also orders sm_de / sm_au
   if (threadIdx.x == 0) atomicAdd(gdcatt, dc_blk);
   for (int i = threadIdx.x; i < A; i += blockDim.x) {
-    const bf16_t* prow = pc_buf + ((long)b * A + i) * Tpad8;
+    const float* prow = pc_buf + ((long)b * A + i) * Tpad8;
     const float ua = Uatt[i];
     float sps = 0.f, sdw = 0.f, sua = 0.f;
     int s = sbeg;
     const int a8beg = (sbeg + 7) & ~7;
     const int a8end = send & ~7;
     for (; s < min(a8beg, send); ++s) {
-      const float pc = (float)prow[s];
+      const float pc = prow[s];
       const float de = sm_de[s - sbeg];
       const float dpc = de * (1.f - pc * pc) * ua;
       sps += dpc;
@@ -809,10 +810,12 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
       sua += de * pc;
     }
     for (; s + 8 <= a8end; s += 8) {
-      bf16x8 pv = *(const bf16x8*)(prow + s);
+      const float4 p0 = *(const float4*)(prow + s);
+      const float4 p1 = *(const float4*)(prow + s + 4);
+      const float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float pc = (float)pv[k];
+        const float pc = pv[k];
         const float de = sm_de[s + k - sbeg];
         const float dpc = de * (1.f - pc * pc) * ua;
         sps += dpc;
@@ -821,7 +824,7 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
       }
     }
     for (; s < send; ++s) {
-      const float pc = (float)prow[s];
+      const float pc = prow[s];
       const float de = sm_de[s - sbeg];
       const float dpc = de * (1.f - pc * pc) * ua;
       sps += dpc;
@@ -867,7 +870,9 @@ std::vector<torch::Tensor> cond_gru_fwd(
   auto ctxs_all = torch::empty({T, B, C}, optsF);
   auto alphas_all = torch::empty({T, B, Ts}, optsF);
   auto saved2 = torch::empty({T, B, 3 * H}, optsB);
-  auto saved1 = torch::empty({T, B, 4 * H}, optsB);
+  // fp32: the backward forms 1 - u, u(1 - u), 1 - hbar^2 from these; from
+  // bf16 copies a saturated gate loses all relative precision in them
+  auto saved1 = torch::empty({T, B, 4 * H}, optsF);
   auto pstate_all = torch::empty({T, B, A}, optsF);
   auto ctxpre_all = torch::empty({T, B, C}, optsB);
   auto accA_used = torch::empty({T, B, Ts}, optsF);
@@ -983,7 +988,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
                          b1.data_ptr<float>(), bx1.data_ptr<float>(), mt,
                          h2_all.data_ptr<float>() + (long)t * B * H,
                          h2bf_p + ((t + 1) % 2) * hbstride, Hpad,
-                         (bf16_t*)saved1.data_ptr() + (long)t * B * 4 * H, B,
+                         saved1.data_ptr<float>() + (long)t * B * 4 * H, B,
                          H, Hpad);
     } else {
       hipLaunchKernelGGL(cond_gru1_step_fwd, dim3(ngrpH), dim3(1024), 0,
@@ -993,7 +998,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
                          bx1.data_ptr<float>(), mt,
                          h2_all.data_ptr<float>() + (long)t * B * H,
                          h2bf_p + ((t + 1) % 2) * hbstride, Hpad,
-                         (bf16_t*)saved1.data_ptr() + (long)t * B * 4 * H, B,
+                         saved1.data_ptr<float>() + (long)t * B * 4 * H, B,
                          H, K1);
     }
   }
@@ -1055,8 +1060,7 @@ std::vector<torch::Tensor> cond_gru_bwd(
   auto dal_buf = torch::empty({Ts, B}, optsF);
   auto dot_buf = torch::empty({B}, optsF);
   const int Tpad8 = (Ts + 7) / 8 * 8;
-  auto pc_buf = torch::empty({B, A, Tpad8},
-                             dh2_all.options().dtype(torch::kBFloat16));
+  auto pc_buf = torch::empty({B, A, Tpad8}, optsF);
   const int Apad = Apad32;
   auto dstep1 = torch::zeros({32, K3Hpad}, optsB);
   auto dstepC = torch::zeros({32, K3Hpad}, optsB);
@@ -1084,7 +1088,7 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        stream, dh_carry.data_ptr<float>(),
                        dh_carry.data_ptr<float>() + (long)B * H,
                        dh2_c.data_ptr<float>() + (long)t * B * H,
-                       (const bf16_t*)saved1.data_ptr() + (long)t * B * 4 * H,
+                       saved1.data_ptr<float>() + (long)t * B * 4 * H,
                        h1_all.data_ptr<float>() + (long)t * B * H,
                        bx1.data_ptr<float>(), mt,
                        (bf16_t*)dstep1.data_ptr(), (bf16_t*)dstepC.data_ptr(),
@@ -1140,14 +1144,14 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        accA_used.data_ptr<float>() + (long)t * B * Ts,
                        Dwei.data_ptr<float>(), Uatt.data_ptr<float>(),
                        daccA.data_ptr<float>(), dpctx_acc.data_ptr<float>(),
-                       (bf16_t*)pc_buf.data_ptr(), B, Ts, A, Tpad8);
+                       pc_buf.data_ptr<float>(), B, Ts, A, Tpad8);
     const int RSCH = std::max(1, std::min(12, Ts / 64));
     hipLaunchKernelGGL(cond_attn_bwd_reduce, dim3(B, RSCH), dim3(256),
                        2 * ((Ts + RSCH - 1) / RSCH) * sizeof(float), stream,
                        alphas_all.data_ptr<float>() + (long)t * B * Ts,
                        dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),
                        accA_used.data_ptr<float>() + (long)t * B * Ts,
-                       (const bf16_t*)pc_buf.data_ptr(),
+                       pc_buf.data_ptr<float>(),
                        Uatt.data_ptr<float>(),
                        dpstate_all.data_ptr<float>() + (long)t * B * A,
                        gdDwei.data_ptr<float>(), gdUatt.data_ptr<float>(),

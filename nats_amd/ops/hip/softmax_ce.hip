@@ -28,7 +28,9 @@ __global__ void softmax_ce_fwd_kernel(const bf16_t* __restrict__ logits,
   if (n >= N) return;
   const bf16_t* row = logits + n * V;
 
-  // online max + sum(exp(x - max)) per thread, then block reduce
+  // online max + sum(exp(x - max)) per thread, then block reduce; -inf
+  // logits (masked-out words) are skipped: as a thread's first element one
+  // would meet m = -inf
   float m = -INFINITY, s = 0.f;
   const int64_t V8 = V & ~(int64_t)7;
   for (int64_t v = threadIdx.x * 8; v < V8; v += (int64_t)BLOCK * 8) {
@@ -36,6 +38,7 @@ __global__ void softmax_ce_fwd_kernel(const bf16_t* __restrict__ logits,
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float x = (float)x8[i];
+      if (x == -INFINITY) continue;  // contributes 0; exp(-inf - -inf) = NaN
       if (x > m) {
         s *= __expf(m - x);
         m = x;
@@ -45,6 +48,7 @@ __global__ void softmax_ce_fwd_kernel(const bf16_t* __restrict__ logits,
   }
   for (int64_t v = V8 + threadIdx.x; v < V; v += BLOCK) {
     const float x = (float)row[v];
+    if (x == -INFINITY) continue;
     if (x > m) {
       s *= __expf(m - x);
       m = x;

@@ -5,6 +5,8 @@ import numpy
 import pytest
 import torch
 
+from kernel_ref import _cond_inputs, _gru_inputs, assert_grad_close
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,43 +18,6 @@ def ext():
     return m
 
 
-def assert_grad_close(a, b, name="", rel=0.06, floor_frac=1e-3,
-                      global_scale=None):
-    """Scale-aware gradient comparison.
-
-    Global-max normalization (rel = max|a-b| / max|a|) lets a large
-    relative error on a small-magnitude COLUMN hide under the tensor's
-    largest column. Instead: normalize per output column (last axis —
-    each column of a weight grad is an independent sum over (T,B)), with
-    a small absolute floor of floor_frac * global_max covering bf16
-    swamping where large contributions cancel. floor_frac=1e-3 is ~60x
-    tighter than the old global-max bound for the smallest columns.
-    """
-    a2 = a.reshape(-1, a.shape[-1]) if a.dim() > 1 else a.reshape(1, -1)
-    b2 = b.reshape(-1, b.shape[-1]) if b.dim() > 1 else b.reshape(1, -1)
-    col_scale = a2.abs().amax(dim=0)
-    # global_scale: the MODEL's gradient magnitude — reduce-to-scalar
-    # grads (c_att = sum of thousands of cancelling de terms) carry fp32
-    # accumulation noise proportional to the contributions, not to their
-    # near-zero sum; floor such tensors at 1e-3 of the model scale
-    floor_base = a2.abs().max().clamp_min(1e-6)
-    if global_scale is not None:
-        floor_base = max(float(floor_base), 1e-2 * float(global_scale))
-    floor = floor_frac * floor_base
-    col_err = (a2 - b2).abs().amax(dim=0)
-    bound = rel * col_scale + floor
-    bad = col_err > bound
-    if bool(bad.any()):
-        worst = int((col_err - bound)[bad].argmax())
-        idx = bad.nonzero().flatten()[worst]
-        raise AssertionError(
-            "%s: %d/%d columns out of bound; worst col %d err %.3e vs "
-            "bound %.3e (col scale %.3e, floor %.3e)" % (
-                name, int(bad.sum()), bad.numel(), int(idx),
-                float(col_err[idx]), float(bound[idx]),
-                float(col_scale[idx]), float(floor)))
-
-
 def test_mfma_fragment_layout(ext):
     """Transpose-detecting self-test of the MFMA lane maps (asymmetric B)."""
     torch.manual_seed(0)
@@ -62,19 +27,6 @@ def test_mfma_fragment_layout(ext):
     C = ext.mfma_gemm_bt(A.contiguous(), B.t().contiguous())
     ref = (A.float() @ B.float())
     torch.testing.assert_close(C, ref, rtol=2e-2, atol=2e-2)
-
-
-def _gru_inputs(T=13, B=5, H=48, E=20, seed=0, with_mask=True):
-    g = torch.Generator().manual_seed(seed)
-    xg = torch.randn(T, B, 2 * H, generator=g)
-    xc = torch.randn(T, B, H, generator=g)
-    U = 0.3 * torch.randn(H, 2 * H, generator=g)
-    Ux = 0.3 * torch.randn(H, H, generator=g)
-    mask = None
-    if with_mask:
-        lens = torch.randint(2, T + 1, (B,), generator=g)
-        mask = (torch.arange(T).unsqueeze(1) < lens.unsqueeze(0)).float()
-    return xg, xc, U, Ux, mask
 
 
 @pytest.mark.parametrize("with_mask", [False, True])
@@ -189,33 +141,6 @@ def test_native_extension_is_used_on_gpu():
     assert ops._hip_ext() is not None
     import os
     assert not os.environ.get("NATS_AMD_FORCE_EAGER")
-
-
-def _cond_inputs(T=7, B=5, H=32, Ts=9, A=12, E=10, seed=5, with_masks=True):
-    from nats_amd.models.distraction import NatsModel, default_options
-    torch.manual_seed(seed)
-    g = torch.Generator().manual_seed(seed)
-    C = 2 * H
-    opts = default_options(dim_word=E, dim=H, dim_att=A, n_words=50)
-    model = NatsModel(opts, seed=seed)
-    # inflate the 0.01-scale attention/distraction weights so alpha is far
-    # from uniform and the gate far from linear — otherwise a broken
-    # pstate/gate path can hide inside a near-uniform attention pattern
-    with torch.no_grad():
-        for k in ("decoder_W_att", "decoder_Wc_att", "decoder_U_att",
-                  "decoder_D_wei", "decoder_W_con", "decoder_U_con"):
-            model.P[k].mul_(40.0)
-    yg = torch.randn(T, B, 2 * H, generator=g)
-    yc = torch.randn(T, B, H, generator=g)
-    init = torch.randn(B, H, generator=g) * 0.1
-    ctx = torch.randn(Ts, B, C, generator=g)
-    mask = ctx_mask = None
-    if with_masks:
-        lens = torch.randint(2, T + 1, (B,), generator=g)
-        mask = (torch.arange(T).unsqueeze(1) < lens.unsqueeze(0)).float()
-        slens = torch.randint(2, Ts + 1, (B,), generator=g)
-        ctx_mask = (torch.arange(Ts).unsqueeze(1) < slens.unsqueeze(0)).float()
-    return model, yg, yc, mask, init, ctx, ctx_mask
 
 
 @pytest.mark.parametrize("with_masks", [False, True])

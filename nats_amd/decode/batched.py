@@ -14,7 +14,9 @@ reshuffles are device index_selects; the only per-step host transfers
 are the top-k candidate ids/costs and the selected attention rows for
 the alignment output (two small synchronisations per step — the naive
 numpy bookkeeping round-trip was ~25% of decode time in the kernel
-trace, profiles/decode_kernel_stats.csv).
+trace, profiles/decode_kernel_stats.csv). With ``fused_select=True`` the
+per-sentence top-k loop becomes one ops.beam_select call per step
+(measured in profiles/README.md, "Decode v4").
 
 Numerics note: results are mathematically identical to per-sentence
 gen_sample, but not bitwise — the batched masked-mean init state and
@@ -29,14 +31,80 @@ import math
 import numpy
 import torch
 
+from .. import ops
 from .beam import distraction_penalties_gpu
+
+
+def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
+                  any_lambda, kl_factor, ctx_factor, state_factor):
+    """Phases 1 and 2a of a decode step through ops.beam_select: one upload
+    ([running scores | seg_off | want], the fp32 scores carried as their
+    int32 bits), one selection call for every alive sentence, one copy of
+    the ranks/costs back, one gather of every selected attention row.
+
+    Returns (pend, alpha_sel) exactly as the per-sentence path builds
+    them: pend[j] = (i, sl, tis, wis, costs, sel_dev) per alive sentence,
+    alpha_sel the selected attention rows in pend order (host array)."""
+    device = probs.device
+    V = probs.shape[1]
+    lives = [st[i]["live"] for i in alive]
+    wants = [k - st[i]["dead"] for i in alive]
+    Sa, R, K = len(alive), sum(lives), max(wants)
+    seg = numpy.zeros(Sa + 1, dtype="int32")
+    seg[1:] = numpy.cumsum(lives)
+    prev = numpy.concatenate([st[i]["scores"] for i in alive])
+    tab = torch.from_numpy(numpy.concatenate(
+        [prev.astype("float32").view("int32"), seg,
+         numpy.asarray(wants, dtype="int32")])).to(device)
+    prev_dev = tab[:R].view(torch.float32)
+    seg_dev, want_dev = tab[R:R + Sa + 1], tab[R + Sa + 1:]
+
+    # rerank penalties stay per sentence (zeros where there is no history)
+    penalty = None
+    if ii > 0 and any_lambda:
+        pens = []
+        for j, i in enumerate(alive):
+            sl = slice(int(seg[j]), int(seg[j + 1]))
+            if dstate[i]["ha"] is None:
+                pens.append(torch.zeros(lives[j], device=device))
+                continue
+            pens.append(distraction_penalties_gpu(
+                dstate[i]["ha"], dstate[i]["hc"], dstate[i]["hs"],
+                alpha[sl].float(), ctx_t[sl].float(), h2[sl].float(),
+                kl_factor, ctx_factor, state_factor))
+        penalty = torch.cat(pens)
+
+    ranks_dev, costs_dev = ops.beam_select(
+        probs.float(), prev_dev, seg_dev, want_dev, penalty=penalty,
+        use_unk=use_unk, K=K)
+    # batch row of every selection (padding slots point at row seg[s])
+    rows_dev = ranks_dev.clamp_min(0) // V + seg_dev[:-1, None]
+    sel_host = torch.cat([ranks_dev.double().flatten(),
+                          costs_dev.double().flatten()]).cpu().numpy()
+    alpha_pad = alpha.float()[rows_dev.flatten()].cpu().numpy()
+
+    pend, alpha_rows = [], []
+    for j, i in enumerate(alive):
+        sl = slice(int(seg[j]), int(seg[j + 1]))
+        want = wants[j]
+        ranks = sel_host[j * K:j * K + want].astype(numpy.int64)
+        costs = sel_host[(Sa + j) * K:(Sa + j) * K + want].astype("float32")
+        pend.append((i, sl, ranks // V, ranks % V, costs,
+                     rows_dev[j, :want]))
+        alpha_rows.append(alpha_pad[j * K:j * K + want])
+    return pend, numpy.concatenate(alpha_rows)
 
 
 @torch.no_grad()
 def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                        kl_factor=0.0, ctx_factor=0.0, state_factor=0.0,
-                       use_graph=True):
+                       use_graph=True, fused_select=False):
     """Beam-decode a list of sources jointly.
+
+    fused_select: pick every sentence's candidates with one
+    ops.beam_select call per step (one table upload, one result copy)
+    instead of the per-sentence topk loop. Same keys; exactly equal keys
+    go to the lower flat index (topk leaves that choice open). Opt-in.
 
     xs: list of (T_i, 1) int64 tensors (same device as model).
     maxlen: an int, or a per-sentence list (serving: each request brings
@@ -141,51 +209,58 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 sample_draw=False)
         V = probs.shape[1]
 
-        # ---- phase 1: per-sentence top-k ON DEVICE, one host transfer ----
-        logp = probs.float().log()
-        if not use_unk:
-            logp[:, 1] = NEG_UNK
-        sel_parts = []   # per alive sentence: (ranks (want,), costs (want,))
-        row0 = 0
-        for i in alive:
-            live = st[i]["live"]
-            sl = slice(row0, row0 + live)
-            row0 += live
-            cand = torch.as_tensor(st[i]["scores"],
-                                   device=device)[:, None] - logp[sl]
-            cand_flat = cand.flatten()
-            want = k - st[i]["dead"]
-            sel_flat = cand_flat
-            if ii > 0 and any_lambda and dstate[i]["ha"] is not None:
-                pen = distraction_penalties_gpu(
-                    dstate[i]["ha"], dstate[i]["hc"], dstate[i]["hs"],
-                    alpha[sl].float(), ctx_t[sl].float(), h2[sl].float(),
-                    kl_factor, ctx_factor, state_factor)
-                sel_flat = (cand + pen[:, None]).flatten()
-            ranks = sel_flat.topk(want, largest=False).indices
-            sel_parts.append((ranks, cand_flat[ranks]))  # UN-reranked costs
-        flat_host = torch.cat([torch.cat([r.double(), c.double()])
-                               for r, c in sel_parts]).cpu().numpy()
+        if fused_select:
+            pend, alpha_sel = _select_fused(
+                st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
+                any_lambda, kl_factor, ctx_factor, state_factor)
+        else:
+            # -- phase 1: per-sentence top-k ON DEVICE, one host transfer --
+            logp = probs.float().log()
+            if not use_unk:
+                logp[:, 1] = NEG_UNK
+            # per alive sentence: (ranks (want,), costs (want,))
+            sel_parts = []
+            row0 = 0
+            for i in alive:
+                live = st[i]["live"]
+                sl = slice(row0, row0 + live)
+                row0 += live
+                cand = torch.as_tensor(st[i]["scores"],
+                                       device=device)[:, None] - logp[sl]
+                cand_flat = cand.flatten()
+                want = k - st[i]["dead"]
+                sel_flat = cand_flat
+                if ii > 0 and any_lambda and dstate[i]["ha"] is not None:
+                    pen = distraction_penalties_gpu(
+                        dstate[i]["ha"], dstate[i]["hc"], dstate[i]["hs"],
+                        alpha[sl].float(), ctx_t[sl].float(), h2[sl].float(),
+                        kl_factor, ctx_factor, state_factor)
+                    sel_flat = (cand + pen[:, None]).flatten()
+                ranks = sel_flat.topk(want, largest=False).indices
+                # UN-reranked costs
+                sel_parts.append((ranks, cand_flat[ranks]))
+            flat_host = torch.cat([torch.cat([r.double(), c.double()])
+                                   for r, c in sel_parts]).cpu().numpy()
 
-        # ---- phase 2: bookkeeping + device-side state reshuffle ----
-        alpha_gather = []   # device rows to fetch for alignment histories
-        pend = []           # (i, sl, tis, wis, costs, sel_dev)
-        row0 = 0
-        off = 0
-        for i in alive:
-            live = st[i]["live"]
-            sl = slice(row0, row0 + live)
-            row0 += live
-            want = k - st[i]["dead"]
-            ranks = flat_host[off:off + want].astype(numpy.int64)
-            costs = flat_host[off + want:off + 2 * want].astype("float32")
-            off += 2 * want
-            tis = ranks // V
-            wis = ranks % V
-            sel_dev = torch.as_tensor(tis, device=device) + sl.start
-            alpha_gather.append(alpha.float()[sel_dev])
-            pend.append((i, sl, tis, wis, costs, sel_dev))
-        alpha_sel = torch.cat(alpha_gather).cpu().numpy()
+            # -- phase 2: bookkeeping + device-side state reshuffle --
+            alpha_gather = []   # device rows to fetch for alignments
+            pend = []           # (i, sl, tis, wis, costs, sel_dev)
+            row0 = 0
+            off = 0
+            for i in alive:
+                live = st[i]["live"]
+                sl = slice(row0, row0 + live)
+                row0 += live
+                want = k - st[i]["dead"]
+                ranks = flat_host[off:off + want].astype(numpy.int64)
+                costs = flat_host[off + want:off + 2 * want].astype("float32")
+                off += 2 * want
+                tis = ranks // V
+                wis = ranks % V
+                sel_dev = torch.as_tensor(tis, device=device) + sl.start
+                alpha_gather.append(alpha.float()[sel_dev])
+                pend.append((i, sl, tis, wis, costs, sel_dev))
+            alpha_sel = torch.cat(alpha_gather).cpu().numpy()
 
         arow = 0
         for i, sl, tis, wis, costs, sel_dev in pend:

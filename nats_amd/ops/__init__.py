@@ -220,6 +220,104 @@ def embed_gather(Wemb, ids, shift=False):
     return emb
 
 
+BEAM_SELECT_MAX_K = 32  # winners a selection block keeps (beam_select.hip)
+
+
+def _host_ints(t):
+    """Values of a segment table the host can read for free: a list, or a
+    CPU tensor. None for a device tensor (reading it would sync)."""
+    if not torch.is_tensor(t):
+        return [int(v) for v in t]
+    if t.dtype != torch.int32 or t.dim() != 1:
+        raise TypeError("beam_select: seg_off and want must be 1-d int32, "
+                        "got %s %s" % (t.dtype, tuple(t.shape)))
+    return None if t.is_cuda else t.tolist()
+
+
+def beam_select(probs, prev_cost, seg_off, want, penalty=None, use_unk=True,
+                K=None):
+    """Per-sentence beam candidate selection in one call: the ``want[s]``
+    smallest ``(prev_cost[r] - log(probs[r, w])) + penalty[r]`` over the
+    rows ``[seg_off[s], seg_off[s+1])`` of sentence ``s``, ascending, ties
+    to the lower flat index ``local_row*V + w``, NaN after +inf.
+
+    probs (R,V) fp32 contiguous; prev_cost (R,) fp32; seg_off (S+1,) and
+    want (S,) int32; penalty (R,) fp32 or None. ``seg_off``/``want`` may be
+    lists or CPU tensors (validated here, then moved to ``probs.device`` in
+    one copy) or tensors already on the device; the latter cannot be read
+    without a sync, so ``K = max(want)`` must then be passed and the caller
+    vouches for ``1 <= want[s] <= min(K, live_s*V)`` and ``live_s*V < 2**31``.
+
+    Returns (ranks (S,K) int64, -1 beyond want[s]; costs (S,K) fp32, +inf
+    beyond want[s]). costs are the UN-reranked candidate costs, recomputed
+    from prev_cost and probs (nats.py:1004 cand_flat[ranks]).
+    Semantics: nats.py:1001-1004 per sentence; use_unk=False pins word 1 to
+    log-probability log(1e-20).
+    """
+    if probs.dim() != 2 or probs.dtype != torch.float32:
+        raise TypeError("beam_select: probs must be (R, V) float32, got %s %s"
+                        % (probs.dtype, tuple(probs.shape)))
+    R, V = probs.shape
+    for name, t in (("prev_cost", prev_cost), ("penalty", penalty)):
+        if t is not None and (t.dtype != torch.float32 or t.shape != (R,)):
+            raise TypeError("beam_select: %s must be (R,) float32, got %s %s"
+                            % (name, t.dtype, tuple(t.shape)))
+    offs, wants = _host_ints(seg_off), _host_ints(want)
+    S = len(want)
+    if len(seg_off) != S + 1 or S < 1:
+        raise ValueError("beam_select: seg_off must have len(want)+1 entries")
+    if K is None:
+        if wants is None:
+            raise ValueError("beam_select: pass K=max(want) when want is a "
+                             "device tensor (deriving it would sync)")
+        K = max(wants)
+    K = int(K)
+    if K > BEAM_SELECT_MAX_K:
+        raise ValueError("beam_select: K=%d exceeds the kernel's %d winners "
+                         "per sentence" % (K, BEAM_SELECT_MAX_K))
+    if offs is not None:
+        if offs[0] != 0 or offs[-1] != R:
+            raise ValueError("beam_select: seg_off must run from 0 to R=%d"
+                             % R)
+        for s in range(S):
+            live = offs[s + 1] - offs[s]
+            if live < 0 or live * V >= 2 ** 31:
+                raise ValueError("beam_select: sentence %d has %d x %d "
+                                 "candidates; the flat index needs live*V "
+                                 "in [0, 2**31)" % (s, live, V))
+    if wants is not None:
+        for s in range(S):
+            if not 1 <= wants[s] <= K:
+                raise ValueError("beam_select: want[%d]=%d outside [1, K=%d]"
+                                 % (s, wants[s], K))
+            if offs is not None and wants[s] > (offs[s + 1] - offs[s]) * V:
+                raise ValueError("beam_select: want[%d]=%d exceeds the "
+                                 "sentence's %d candidates" % (
+                                     s, wants[s],
+                                     (offs[s + 1] - offs[s]) * V))
+    if not probs.is_contiguous():
+        raise ValueError("beam_select: probs must be contiguous (row stride "
+                         "V)")
+    if _use_hip(probs):
+        if offs is not None and wants is not None:
+            tab = torch.tensor(offs + wants, dtype=torch.int32).to(
+                probs.device, non_blocking=True)
+            seg_off, want = tab[:S + 1], tab[S + 1:]
+        else:
+            seg_off = torch.as_tensor(seg_off, dtype=torch.int32,
+                                      device=probs.device)
+            want = torch.as_tensor(want, dtype=torch.int32,
+                                   device=probs.device)
+        ranks, costs = _hip_ext().beam_select(
+            probs, prev_cost.contiguous(), seg_off.contiguous(),
+            want.contiguous(),
+            None if penalty is None else penalty.contiguous(), K,
+            bool(use_unk), eager.NEG_UNK)
+        return ranks, costs
+    return eager.beam_select(probs, prev_cost, seg_off, want, penalty,
+                             use_unk, K)
+
+
 def softmax_xent(logits, targets):
     """Per-position NLL of a softmax over the vocabulary.
 

@@ -7,6 +7,8 @@ autograd) so torch autograd provides the exact BPTT the reference got from
 ``tensor.grad`` (nats.py:1340).
 """
 
+import math
+
 import torch
 
 
@@ -148,3 +150,43 @@ def softmax_xent(logits, targets):
         logits = logits.float()
     logp = torch.log_softmax(logits, dim=-1)
     return -logp.gather(1, targets.unsqueeze(1)).squeeze(1)
+
+
+NEG_UNK = math.log(1e-20)  # log-probability UNK is pinned to (nats.py:1001)
+
+
+def beam_select(probs, prev_cost, seg_off, want, penalty=None, use_unk=True,
+                K=None):
+    """Segmented beam candidate selection (nats.py:1001-1004 per sentence).
+
+    probs (R,V) fp32; prev_cost (R,); seg_off (S+1,) / want (S,) int32
+    tensors or lists: rows [seg_off[s], seg_off[s+1]) are sentence s's live
+    hypotheses; penalty (R,) or None. Candidate cost c = prev_cost[:, None]
+    - log(probs) (word 1 pinned to -log(1e-20) unless use_unk), selection
+    key c + penalty[:, None]. Per sentence the want[s] smallest keys in
+    ascending order, ties to the lower flat index local_row*V + w, NaN
+    after +inf — a stable sort of the flattened keys gives all three.
+
+    Returns (ranks (S,K) int64 padded with -1, costs (S,K) fp32 padded
+    with +inf); costs are the UN-reranked c at the selected candidates.
+    """
+    offs = [int(v) for v in (seg_off.tolist() if torch.is_tensor(seg_off)
+                             else seg_off)]
+    wants = [int(v) for v in (want.tolist() if torch.is_tensor(want)
+                              else want)]
+    S = len(wants)
+    K = max(wants) if K is None else int(K)
+    logp = probs.log()
+    if not use_unk:
+        logp[:, 1] = NEG_UNK
+    cand = prev_cost[:, None] - logp
+    key = cand if penalty is None else cand + penalty[:, None]
+    ranks = torch.full((S, K), -1, dtype=torch.int64, device=probs.device)
+    costs = torch.full((S, K), float("inf"), dtype=probs.dtype,
+                       device=probs.device)
+    for s in range(S):
+        sl = slice(offs[s], offs[s + 1])
+        order = torch.sort(key[sl].flatten(), stable=True).indices[:wants[s]]
+        ranks[s, :wants[s]] = order
+        costs[s, :wants[s]] = cand[sl].flatten()[order]
+    return ranks, costs

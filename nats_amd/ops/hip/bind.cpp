@@ -34,6 +34,12 @@ torch::Tensor rerank_penalties(torch::Tensor hist_a, torch::Tensor hist_c,
                                torch::Tensor hist_s, torch::Tensor cur_a,
                                torch::Tensor cur_c, torch::Tensor cur_s,
                                double kl_f, double ctx_f, double state_f);
+std::vector<torch::Tensor> beam_select(torch::Tensor probs,
+                                       torch::Tensor prev_cost,
+                                       torch::Tensor seg_off,
+                                       torch::Tensor want,
+                                       c10::optional<torch::Tensor> penalty,
+                                       long K, bool use_unk, double neg_unk);
 void fused_adadelta_step(torch::Tensor ptrs, torch::Tensor sizes,
                          torch::Tensor chunk_tensor, torch::Tensor chunk_off,
                          torch::Tensor g2, double clip_c, double rho,
@@ -99,6 +105,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "XCD-constrained grid barrier us/iteration");
   m.def("rerank_penalties", &rerank_penalties,
         "fused decode-time distraction rerank reductions");
+  m.def("beam_select", &beam_select,
+        "segmented beam candidate selection (tile pass + merge pass)");
   m.def("fused_adadelta_step", &fused_adadelta_step,
         "fused multi-tensor global-norm clip + adadelta");
   m.def("cond_gru_fwd", &cond_gru_fwd, "fused cond-GRU decoder forward");

@@ -112,6 +112,31 @@ __device__ __forceinline__ float block_reduce_max(float v) {
   return block_reduce<true>(v);
 }
 
+// Block-wide unsigned 64-bit min, result in every thread, ONE barrier per
+// call: a wave butterfly, one LDS slot per wave, then every thread combines
+// the slots itself. Consecutive calls must alternate ``parity`` (0/1): the
+// slots are double-buffered, so a call's writes cannot land in the buffer
+// the previous call is still reading, and its own barrier orders the call
+// before that one.
+__device__ __forceinline__ unsigned long long block_min_u64(
+    unsigned long long v, int parity) {
+  __shared__ unsigned long long red64[2][NATS_MAX_WAVES];
+#pragma unroll
+  for (int off = NATS_WAVE / 2; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off);
+    v = o < v ? o : v;
+  }
+  if ((threadIdx.x & (NATS_WAVE - 1)) == 0)
+    red64[parity][threadIdx.x / NATS_WAVE] = v;
+  __syncthreads();
+  unsigned long long r = red64[parity][0];
+  for (int w = 1; w < (int)blockDim.x / NATS_WAVE; ++w) {
+    const unsigned long long o = red64[parity][w];
+    r = o < r ? o : r;
+  }
+  return r;
+}
+
 // 4-deep software-pipelined MFMA K-loop: four iterations' fragment loads
 // (both operands) stay in flight ahead of each MFMA so the L2 latency of
 // the 16 scattered 16B lines per fragment amortises over 4 iterations.

@@ -37,13 +37,14 @@ class SummarizerService:
     a single worker thread owns the model/GPU and drains the queue in
     batches of up to ``max_batch`` (default: 64 // k beam rows fit the
     kernel launch), waiting at most ``max_wait_ms`` for co-batchable
-    requests once one is pending.
+    requests once one is pending. ``fused_select`` picks each step's beam
+    candidates with one ops.beam_select call (gen_sample_batched).
     """
 
     def __init__(self, model_path, dictionary, device=None, k=10, maxlen=100,
                  normalize=True, kl_factor=0.0, ctx_factor=0.0,
                  state_factor=0.0, chr_level=False, max_batch=None,
-                 max_wait_ms=5.0):
+                 max_wait_ms=5.0, fused_select=False):
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = device
@@ -54,6 +55,7 @@ class SummarizerService:
         self.ctx_factor = float(ctx_factor)
         self.state_factor = float(state_factor)
         self.chr_level = bool(chr_level)
+        self.fused_select = bool(fused_select)
         self.max_batch = int(max_batch or max(1, 64 // self.k))
         self.max_wait_s = float(max_wait_ms) / 1000.0
         self.model_path = str(model_path)
@@ -183,7 +185,8 @@ class SummarizerService:
                 self.model, xs, k=self.k,
                 maxlen=maxlens if maxlens else self.maxlen, use_unk=True,
                 kl_factor=self.kl_factor, ctx_factor=self.ctx_factor,
-                state_factor=self.state_factor)
+                state_factor=self.state_factor,
+                fused_select=self.fused_select)
         results = []
         for src_words, (sample, score, alphas) in zip(srcs, outs):
             score = numpy.array(score, dtype=numpy.float64)

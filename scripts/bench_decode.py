@@ -20,17 +20,19 @@ from nats_amd.decode.beam import gen_sample
 from nats_amd.models.distraction import NatsModel, default_options
 
 
-def run(model, xs, k, maxlen, use_graph, lam, batched=False):
+def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False):
     n_tokens = 0
     t0 = time.perf_counter()
     if batched:
         from nats_amd.decode.batched import gen_sample_batched
+        extra = {"fused_select": True} if fused else {}
         sb = max(1, 64 // k)
         for base in range(0, len(xs), sb):
             outs = gen_sample_batched(model, xs[base:base + sb], k=k,
                                       maxlen=maxlen, use_unk=True,
                                       kl_factor=lam, ctx_factor=lam,
-                                      state_factor=lam, use_graph=use_graph)
+                                      state_factor=lam, use_graph=use_graph,
+                                      **extra)
             for sample, _, _ in outs:
                 n_tokens += sum(len(s) for s in sample)
     else:
@@ -75,9 +77,17 @@ def main():
         variants.append(("beam+batched+hipgraph", True, 0.0, True))
         variants.append(("beam+distraction+batched+hipgraph", True, 0.5,
                          True))
-    for name, graph, lam, batched in variants:
-        run(model, xs[:2], args.k, args.maxlen, graph, lam, batched)
-        sps, ntok = run(model, xs, args.k, args.maxlen, graph, lam, batched)
+    variants = [v + (False,) for v in variants]
+    # fused candidate selection (ops.beam_select), appended last
+    graph = device == "cuda"
+    suffix = "+hipgraph+fusedselect" if graph else "+fusedselect"
+    variants.append(("beam+batched" + suffix, graph, 0.0, True, True))
+    variants.append(("beam+distraction+batched" + suffix, graph, 0.5, True,
+                     True))
+    for name, graph, lam, batched, fused in variants:
+        run(model, xs[:2], args.k, args.maxlen, graph, lam, batched, fused)
+        sps, ntok = run(model, xs, args.k, args.maxlen, graph, lam, batched,
+                        fused)
         print(json.dumps({
             "metric": "summaries_per_sec", "variant": name, "value": sps,
             "beam": args.k, "n": args.n, "src_len": args.src,

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("-c", "--chr-level", action="store_true")
     ap.add_argument("--max-batch", type=int, default=None)
     ap.add_argument("--max-wait-ms", type=float, default=5.0)
+    ap.add_argument("--fused-select", action="store_true",
+                    help="one fused candidate-selection op per decode step")
     args = ap.parse_args()
 
     import uvicorn
@@ -42,7 +44,8 @@ def main():
         maxlen=args.maxlen, normalize=args.normalize,
         kl_factor=args.kl_factor, ctx_factor=args.ctx_factor,
         state_factor=args.state_factor, chr_level=args.chr_level,
-        max_batch=args.max_batch, max_wait_ms=args.max_wait_ms)
+        max_batch=args.max_batch, max_wait_ms=args.max_wait_ms,
+        fused_select=args.fused_select)
     app = create_app(service)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 

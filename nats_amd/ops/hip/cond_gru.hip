@@ -1,16 +1,23 @@
 // Fused conditional-GRU decoder (training scan + one-step) for gfx950.
 //
 // Implements the reference's gru_cond_layer step (nats.py:498-572; kernel
-// rows K10-K16 in SURVEY §2.4) as five fused kernels per timestep driven
+// rows K10-K16 in SURVEY §2.4) as five fused stages per timestep driven
 // by a C++ time loop (no python in the scan):
 //   1. GRU_2          — reuses nats_gru_step_fwd (identical cell math)
-//   2. pstate GEMM    — h1 @ W_att (small MFMA GEMM)
-//   3. attention      — e-scores + distraction-over-weights + masked
-//                       softmax + acc_alpha update, one WG per batch row
-//   4. context        — weighted sum over source + distraction gate over
-//                       content vectors + acc_ctx update
+//   2. pstate GEMM    — h1 @ W_att (small MFMA GEMM, cond_small_gemm_bt)
+//   3. attention 1    — cond_attn_fwd_chunk, one WG per (batch row,
+//                       s-chunk): e-scores + distraction-over-weights,
+//                       chunk-local masked softmax statistics (online
+//                       softmax), unnormalised partial weighted context
+//   4. attention 2    — cond_attn_combine_gate: global softmax statistics,
+//                       combined context + distraction gate over content
+//                       vectors + acc_ctx update, normalised alphas +
+//                       acc_alpha update
 //   5. GRU_1          — 4-output-group MFMA ([h1|ctx] packed operand) +
 //                       gates/mask pointwise
+// The attention backward is cond_attn_bwd_dalpha (one wave per (b, s)
+// context row) and cond_attn_bwd_fused (one WG per (b, s-chunk): softmax
+// backward, tanh backward into dpctx/acc_alpha, column sums through LDS).
 // The backward pass is the exact reverse chain with the running-sum
 // accumulators' (acc_ctx/acc_alpha) gradients threaded backwards
 // (SURVEY §7 "hard parts" (ii)); weight gradients that factor over time
@@ -22,20 +29,25 @@
 // its K dimension across extra grid dimensions and the elementwise
 // reductions chunk their serial axis, with fp32 partials summed by the
 // NEXT kernel in the chain rather than an extra pass (gru1/gru2 split-K
-// -> pointwise combine; pstate split-K -> escore/softmax inline sums;
-// escore/scatter A-chunks -> e_buf/daccA atomics; dh_carry split-K ->
-// next step's GRU_1 pointwise sums the halves). Scratch that is
-// atomically accumulated each step (e_buf, ctxpre_f32) is re-zeroed by
-// its consumer in the same pass, so the steady-state loop launches no
-// memsets.
+// -> pointwise combine; pstate split-K -> inline sums in both attention
+// passes; attention s-chunks -> per-chunk (max, sum) pairs and partial
+// contexts combined by pass 2; dh_carry split-K -> next step's GRU_1
+// pointwise sums the halves). Every per-step scratch buffer is fully
+// overwritten with plain stores by its producer, so the steady-state loop
+// launches no memsets and no scratch needs re-zeroing. The only float
+// atomics left in the attention chain are the per-chunk adds into
+// dpstate; dD_wei / dU_att / dc_att accumulate over the time loop in one
+// slot per (b, chunk) block and are summed once after it.
 //
 // Round-2 fusions (each GPU-measured; negatives reverted in history):
-// the dctx passthrough + dot-buffer zeroing merged into the GRU_1
-// backward pointwise; the distraction-gate backward plus the
-// dU_con/dW_con column reductions live in the dctx GEMM's epilogue;
-// dh1 += dpstate @ W_att converts fp32 A-fragments in-register; the
-// e-score kernel stages the combined pstate + attention vectors in LDS.
-// Ladder and profiles in profiles/README.md.
+// the dctx passthrough merged into the GRU_1 backward pointwise; the
+// distraction-gate backward plus the dU_con/dW_con column reductions live
+// in the dctx GEMM's epilogue; dh1 += dpstate @ W_att converts fp32
+// A-fragments in-register; the attention kernels stage the combined
+// pstate + attention vectors in LDS. The chunked attention forward and
+// the one-pass attention backward replaced seven kernels by three
+// ("Decoder attention fusion"). Ladder and profiles in
+// profiles/README.md.
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -51,8 +63,8 @@ namespace {
 // A = [32][ldK] bf16 (zero-padded), Bt = [Npad][ldK] bf16. Split-K over
 // grid.z into Cpart [KS][32][N] f32 partials (the unsplit version was 14
 // waves on the whole chip, 11.3us of pure load latency): consumers
-// (cond_attn_escore inline, cond_attn_softmax for the saved pstate_all)
-// sum the KS partials.
+// (cond_attn_fwd_chunk inline, cond_attn_combine_gate for the saved
+// pstate_all) sum the KS partials.
 __global__ void cond_small_gemm_bt(const bf16_t* __restrict__ A,
                                    const bf16_t* __restrict__ Bt,
                                    float* __restrict__ Cpart, int B, int N,
@@ -78,12 +90,59 @@ __global__ void cond_small_gemm_bt(const bf16_t* __restrict__ A,
   }
 }
 
-// ---------------- attention e-scores (s-parallel) ----------------
-// grid (B, ceil(Ts/256), ACH): thread = one source position s, grid.z
-// chunks the A (attention-dim) loop; chunks atomicAdd into e_buf, which
-// arrives ZEROED (cond_attn_softmax re-zeroes it after its last read, so
-// no per-step memset). pstate arrives as [KS][32][A] split-K partials.
-__global__ __launch_bounds__(256) void cond_attn_escore(
+// ---------------- attention: chunking of the source axis ----------------
+// The forward and backward attention kernels run one 256-thread block per
+// (batch row, contiguous s-chunk). A chunk holds at most ATT_CH_MAX source
+// positions (the LDS tiles are sized for it).
+constexpr int ATT_CH_MAX = 64;
+constexpr int ATT_THREADS = 256;
+
+// Chunk length: about one block per CU (256 of them) — B * Ts / 256
+// positions per block — but never more than ATT_CH_MAX (the per-chunk
+// partials stay ~3 % of the context traffic at 64) and never fewer than
+// 16 (below that the [B][NCH][C] partials cost more than the context rows
+// they summarise), rounded up to a multiple of 8. CNN/DM (B 20, Ts 801):
+// 64 -> 13 chunks, 260 blocks; LCSTS (Ts 121) and one-step decode at a
+// short source: 16 -> 8 chunks per row.
+static inline int attn_chunk_len(int B, int Ts) {
+  const long per = ((long)B * Ts + 255) / 256;
+  const int ch = (int)std::min<long>(ATT_CH_MAX, std::max<long>(16, per));
+  return (ch + 7) & ~7;
+}
+
+// Lanes that share one source position in the per-(s, i) loops: the
+// largest power of two in [4, 16] that still gives every position of a
+// chunk its own lane group (chunk 64 -> 4, 32 -> 8, 16 -> 16).
+static inline int attn_lanes_per_s(int CH) {
+  int lps = 4;
+  while (lps < 16 && CH * lps * 2 <= ATT_THREADS) lps *= 2;
+  return lps;
+}
+
+// Stage the combined pstate (sum of the split-K partials, or the saved
+// combined row when PS_KS == 1 and ld == A) and the two attention vectors
+// in LDS: [A] ps | [A] Dwei | [A] Uatt. Caller barriers.
+__device__ __forceinline__ void attn_stage_vectors(
+    float* sm, const float* __restrict__ ps_part, int PS_KS, long ks_stride,
+    int b, const float* __restrict__ Dwei, const float* __restrict__ Uatt,
+    int A) {
+  for (int i = threadIdx.x; i < A; i += blockDim.x) {
+    float ps = 0.f;
+    for (int k = 0; k < PS_KS; ++k)
+      ps += ps_part[(long)k * ks_stride + (long)b * A + i];
+    sm[i] = ps;
+    sm[A + i] = Dwei[i];
+    sm[2 * A + i] = Uatt[i];
+  }
+}
+
+// ---------------- attention forward, pass 1 (one block per (b, chunk)) ----
+// e-scores of the chunk (all of A in the block: no A-split, no atomics),
+// chunk-local softmax statistics, and the chunk's partial weighted context
+// with the UNNORMALISED p = exp(e - m_c) * mask. cond_attn_combine_gate
+// rescales by exp(m_c - M) / L. pstate arrives as [KS][32][A] split-K
+// partials.
+__global__ __launch_bounds__(ATT_THREADS) void cond_attn_fwd_chunk(
     const float* __restrict__ pctx,      // [Ts][B][A]
     const float* __restrict__ ps_part,   // [KS][32][A] pstate partials
     int PS_KS,
@@ -91,136 +150,149 @@ __global__ __launch_bounds__(256) void cond_attn_escore(
     const float* __restrict__ Dwei,      // [A]
     const float* __restrict__ Uatt,      // [A]
     const float* __restrict__ catt_p,    // [1]
-    float* __restrict__ e_buf,           // [Ts][B]
-    int B, int Ts, int A) {
-  // combined pstate + Dwei/Uatt staged in LDS once per block: the inner
-  // i-loop otherwise issues PS_KS+2 extra L2 loads per element for every
-  // one of this block's 256 s-positions
-  extern __shared__ float sm_e[];  // [A] ps, [A] Dwei, [A] Uatt
-  float* sm_ps = sm_e;
-  float* sm_dw = sm_e + A;
-  float* sm_ua = sm_e + 2 * A;
+    const float* __restrict__ ctx_mask,  // [Ts][B] or null
+    const bf16_t* __restrict__ ctx_bf,   // [Ts][B][C]
+    float* __restrict__ alphas_t,        // [B][Ts] out: unnormalised p
+    float* __restrict__ stats,           // [B][NCH][2] out: (m_c, l_c)
+    float* __restrict__ ctx_part,        // [B][NCH][C] out
+    int B, int Ts, int A, int C, int CH, int lps) {
+  extern __shared__ __attribute__((aligned(16))) float sm_att[];  // [3A]
+  __shared__ float sm_e[ATT_CH_MAX];
+  __shared__ float sm_p[ATT_CH_MAX];
+  const float* sm_ps = sm_att;
+  const float* sm_dw = sm_att + A;
+  const float* sm_ua = sm_att + 2 * A;
   const int b = blockIdx.x;
-  for (int i = threadIdx.x; i < A; i += blockDim.x) {
-    float ps = 0.f;
-    for (int k = 0; k < PS_KS; ++k) ps += ps_part[((long)k * 32 + b) * A + i];
-    sm_ps[i] = ps;
-    sm_dw[i] = Dwei[i];
-    sm_ua[i] = Uatt[i];
+  const int NCH = gridDim.y;
+  const int sbeg = blockIdx.y * CH;
+  const int n = min(CH, Ts - sbeg);  // >= 1: NCH = ceil(Ts / CH)
+  attn_stage_vectors(sm_att, ps_part, PS_KS, (long)32 * A, b, Dwei, Uatt, A);
+  __syncthreads();
+
+  // e-scores: lps lanes share one s and walk its pctx row together
+  const int gl = threadIdx.x % lps;
+  const int ngrp = ATT_THREADS / lps;
+  for (int ls = threadIdx.x / lps; ls < n; ls += ngrp) {
+    const int s = sbeg + ls;
+    // masked positions must not influence any max: they are zeroed AFTER
+    // exp, but a padded position's e shifting a max changes rounding for
+    // the real ones — decode results would then depend on how far the
+    // source was padded (the graph-decode length bucketing pads to 64)
+    const bool live =
+        (ctx_mask == nullptr) || ctx_mask[(long)s * B + b] != 0.f;
+    float e = 0.f;
+    if (live) {  // uniform over the lane group
+      const float accAu = accA[(long)b * Ts + s];
+      const float* prow = pctx + ((long)s * B + b) * A;
+      if (A % 4 == 0) {
+        for (int i = gl * 4; i < A; i += lps * 4) {
+          const float4 p = *(const float4*)(prow + i);
+          const float4 st = *(const float4*)(sm_ps + i);
+          const float4 dw = *(const float4*)(sm_dw + i);
+          const float4 ua = *(const float4*)(sm_ua + i);
+          e += tanhf(p.x + st.x + accAu * dw.x) * ua.x +
+               tanhf(p.y + st.y + accAu * dw.y) * ua.y +
+               tanhf(p.z + st.z + accAu * dw.z) * ua.z +
+               tanhf(p.w + st.w + accAu * dw.w) * ua.w;
+        }
+      } else {
+        for (int i = gl; i < A; i += lps)
+          e += tanhf(prow[i] + sm_ps[i] + accAu * sm_dw[i]) * sm_ua[i];
+      }
+    }
+    for (int off = lps / 2; off > 0; off >>= 1) e += __shfl_xor(e, off);
+    if (gl == 0) sm_e[ls] = live ? e + catt_p[0] : -INFINITY;
   }
   __syncthreads();
-  const int s = blockIdx.y * blockDim.x + threadIdx.x;
-  if (s >= Ts) return;
-  const int ACH = gridDim.z;
-  const int chunkA = ((A + ACH - 1) / ACH + 3) & ~3;
-  const int ibeg = blockIdx.z * chunkA;
-  const int iend = min(A, ibeg + chunkA);
-  if (ibeg >= iend) return;
-  const float accAu = accA[(long)b * Ts + s];
-  const float* prow = pctx + ((long)s * B + b) * A;
-  float e = (blockIdx.z == 0) ? catt_p[0] : 0.f;
-  for (int i = ibeg; i < iend; ++i) {
-    e += tanhf(prow[i] + sm_ps[i] + accAu * sm_dw[i]) * sm_ua[i];
+
+  // chunk-local statistics: n <= 64, so the first wave holds the chunk
+  if (threadIdx.x < NATS_WAVE) {
+    const int ls = threadIdx.x;
+    const float e = (ls < n) ? sm_e[ls] : -INFINITY;
+    float m = e;
+#pragma unroll
+    for (int off = NATS_WAVE / 2; off > 0; off >>= 1)
+      m = fmaxf(m, __shfl_xor(m, off));
+    float p = 0.f;
+    if (e != -INFINITY) {  // live, hence m finite
+      p = __expf(e - m);
+      if (ctx_mask != nullptr) p *= ctx_mask[(long)(sbeg + ls) * B + b];
+    }
+    float l = p;
+#pragma unroll
+    for (int off = NATS_WAVE / 2; off > 0; off >>= 1) l += __shfl_xor(l, off);
+    sm_p[ls] = p;
+    if (ls < n) alphas_t[(long)b * Ts + sbeg + ls] = p;
+    if (ls == 0) {
+      stats[((long)b * NCH + blockIdx.y) * 2] = m;  // -inf: empty chunk
+      stats[((long)b * NCH + blockIdx.y) * 2 + 1] = l;
+    }
   }
-  if (ACH == 1) {
-    e_buf[(long)s * B + b] += e;  // single chunk: still additive (zeroed)
-  } else {
-    atomicAdd(e_buf + (long)s * B + b, e);
+  __syncthreads();
+
+  // partial weighted context: each thread owns 8 consecutive c (one 16 B
+  // load per source row), eight rows in flight per thread
+  float* part = ctx_part + ((long)b * NCH + blockIdx.y) * C;
+  const long sstride = (long)B * C;
+  const bf16_t* cbase = ctx_bf + ((long)sbeg * B + b) * C;
+  const int C8 = C & ~7;
+  for (int c0 = threadIdx.x * 8; c0 < C8; c0 += ATT_THREADS * 8) {
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bf16_t* col = cbase + c0;
+    int ls = 0;
+    for (; ls + 8 <= n; ls += 8) {
+      bf16x8 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        v[u] = *(const bf16x8*)(col + (long)(ls + u) * sstride);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float p = sm_p[ls + u];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += (float)v[u][k] * p;
+      }
+    }
+    for (; ls < n; ++ls) {
+      const bf16x8 v = *(const bf16x8*)(col + (long)ls * sstride);
+      const float p = sm_p[ls];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] += (float)v[k] * p;
+    }
+    if (C % 4 == 0) {  // rows of part are 16 B aligned
+      *(float4*)(part + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      *(float4*)(part + c0 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) part[c0 + k] = acc[k];
+    }
+  }
+  for (int c = C8 + threadIdx.x; c < C; c += ATT_THREADS) {  // C % 8 tail
+    float acc = 0.f;
+    for (int ls = 0; ls < n; ++ls)
+      acc += (float)cbase[(long)ls * sstride + c] * sm_p[ls];
+    part[c] = acc;
   }
 }
 
-// ---------------- softmax finish + acc_alpha update (one WG per b) ----
-__global__ __launch_bounds__(1024) void cond_attn_softmax(
+// ---------------- attention forward, pass 2: combine + gate ----------------
+// grid (B, ceil(C/256)). Every block derives its row's global softmax
+// statistics from the NCH chunk pairs (serially, in chunk order: all blocks
+// of a row agree bit for bit), combines the partial contexts with the
+// per-chunk scale w_c = exp(m_c - M) / L, applies the distraction gate and
+// the acc_ctx update, and finishes its share of the row's attention
+// weights (alphas *= w_chunk, acc_alpha update). Block y == 0 also writes
+// the combined pstate the backward reads.
+__global__ __launch_bounds__(ATT_THREADS) void cond_attn_combine_gate(
+    const float* __restrict__ stats,     // [B][NCH][2]
+    const float* __restrict__ ctx_part,  // [B][NCH][C]
+    int NCH, int CH,
+    float* __restrict__ alphas_t,        // [B][Ts] in: p, out: alpha
     float* __restrict__ accA,            // [B][Ts] in/out
     float* __restrict__ accA_used_t,     // [B][Ts] out (pre-update copy)
-    const float* __restrict__ ctx_mask,  // [Ts][B] or null
-    const float* __restrict__ mask_t,    // [B] or null
-    float* __restrict__ e_buf,           // [Ts][B]; re-zeroed for t+1
-    float* __restrict__ alphas_t,        // [B][Ts] out
     const float* __restrict__ ps_part,   // [KS][32][A] pstate partials
     int PS_KS,
     float* __restrict__ pstate_t,        // [B][A] combined (for backward)
-    int A,
-    int B, int Ts) {
-  { // combine the split-K pstate partials once (backward reads pstate_all)
-    const int b0 = blockIdx.x;
-    for (int i = threadIdx.x; i < A; i += blockDim.x) {
-      float ps = 0.f;
-      for (int k = 0; k < PS_KS; ++k)
-        ps += ps_part[((long)k * 32 + b0) * A + i];
-      pstate_t[(long)b0 * A + i] = ps;
-    }
-  }
-  const int b = blockIdx.x;
-
-  // masked positions must not influence the max: they are zeroed AFTER
-  // exp, but a padded row's e shifting M changes rounding for the real
-  // rows — decode results would then depend on how far the source was
-  // padded (the graph-decode length bucketing pads to 64)
-  float lmax = -INFINITY;
-  for (int s = threadIdx.x; s < Ts; s += blockDim.x) {
-    if (ctx_mask != nullptr && ctx_mask[(long)s * B + b] == 0.f) continue;
-    lmax = fmaxf(lmax, e_buf[(long)s * B + b]);
-  }
-  const float bmax = block_reduce_max(lmax);
-  // all-masked rows cannot occur (every sequence has >= 1 real token),
-  // but guard the degenerate -inf max anyway
-  const float M = isfinite(bmax) ? bmax : 0.f;
-
-  float lsum = 0.f;
-  for (int s = threadIdx.x; s < Ts; s += blockDim.x) {
-    float a = __expf(e_buf[(long)s * B + b] - M);
-    e_buf[(long)s * B + b] = 0.f;  // ready for the next step's atomics
-    if (ctx_mask != nullptr) a *= ctx_mask[(long)s * B + b];
-    alphas_t[(long)b * Ts + s] = a;  // unnormalised, fixed below
-    lsum += a;
-  }
-  const float inv = 1.f / block_reduce_sum(lsum);
-
-  const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-  for (int s = threadIdx.x; s < Ts; s += blockDim.x) {
-    const float al = alphas_t[(long)b * Ts + s] * inv;
-    alphas_t[(long)b * Ts + s] = al;
-    accA_used_t[(long)b * Ts + s] = accA[(long)b * Ts + s];
-    accA[(long)b * Ts + s] += mm * al;
-  }
-}
-
-// ---------------- weighted context: s-chunked partial sums ----------
-// grid (B, ceil(C/256), SCH); f32 atomicAdd into ctxpre_f32 (zeroed per
-// step). Unrolled by 4 over s for memory-level parallelism.
-__global__ void cond_attn_ctx_partial(
-    const bf16_t* __restrict__ ctx_bf,   // [Ts][B][C]
-    const float* __restrict__ alphas_t,  // [B][Ts]
-    float* __restrict__ ctxpre_f32,      // [B][C] (accumulated)
-    int B, int Ts, int C, int SCH) {
-  const int b = blockIdx.x;
-  const int c = blockIdx.y * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const int chunk = (Ts + SCH - 1) / SCH;
-  const int sbeg = blockIdx.z * chunk;
-  const int send = min(Ts, sbeg + chunk);
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int s = sbeg;
-  for (; s + 4 <= send; s += 4) {
-    s0 += (float)ctx_bf[((long)(s + 0) * B + b) * C + c] *
-          alphas_t[(long)b * Ts + s + 0];
-    s1 += (float)ctx_bf[((long)(s + 1) * B + b) * C + c] *
-          alphas_t[(long)b * Ts + s + 1];
-    s2 += (float)ctx_bf[((long)(s + 2) * B + b) * C + c] *
-          alphas_t[(long)b * Ts + s + 2];
-    s3 += (float)ctx_bf[((long)(s + 3) * B + b) * C + c] *
-          alphas_t[(long)b * Ts + s + 3];
-  }
-  for (; s < send; ++s)
-    s0 += (float)ctx_bf[((long)s * B + b) * C + c] *
-          alphas_t[(long)b * Ts + s];
-  atomicAdd(&ctxpre_f32[(long)b * C + c], s0 + s1 + s2 + s3);
-}
-
-// ---------------- distraction gate + acc_ctx update ----------------
-__global__ void cond_attn_gate_fwd(
-    float* __restrict__ ctxpre_f32,  // [B][C]; re-zeroed for t+1's atomics
+    int A, int Ts,
     const float* __restrict__ Ucon, const float* __restrict__ Wcon,
     float* __restrict__ accC,            // [B][C] in/out
     bf16_t* __restrict__ accC_used_t,    // [B][C]
@@ -228,20 +300,58 @@ __global__ void cond_attn_gate_fwd(
     float* __restrict__ ctxs_t,          // [B][C] (gated output)
     bf16_t* __restrict__ hc_bf,          // [32][K1] GRU_1 operand
     int ctx_off, int ldK1, const float* __restrict__ mask_t, int B, int C) {
+  extern __shared__ float sm_w[];  // [NCH] per-chunk scale
   const int b = blockIdx.x;
-  const int c = blockIdx.y * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float sum = ctxpre_f32[(long)b * C + c];
-  ctxpre_f32[(long)b * C + c] = 0.f;  // next step's ctx_partial atomics
-  ctxpre_t[(long)b * C + c] = (bf16_t)sum;
-  const float accCv = accC[(long)b * C + c];
-  accC_used_t[(long)b * C + c] = (bf16_t)accCv;
-  // distraction over input content vectors (nats.py:545-546)
-  const float g = tanhf(Ucon[c] * sum + accCv * Wcon[c]);
-  ctxs_t[(long)b * C + c] = g;
-  hc_bf[(long)b * ldK1 + ctx_off + c] = (bf16_t)g;
+  const float* st = stats + (long)b * NCH * 2;
+  float M = -INFINITY;
+  for (int k = 0; k < NCH; ++k) M = fmaxf(M, st[2 * k]);
+  float L = 0.f;
+  for (int k = 0; k < NCH; ++k) {
+    const float l = st[2 * k + 1];
+    if (l > 0.f) L += l * __expf(st[2 * k] - M);
+  }
+  // all-masked rows cannot occur (every sequence has >= 1 real token),
+  // but guard the degenerate L = 0 anyway: such a row gets alpha = 0
+  const float inv = (L > 0.f) ? 1.f / L : 0.f;
+  for (int k = threadIdx.x; k < NCH; k += blockDim.x)
+    sm_w[k] = (st[2 * k + 1] > 0.f) ? __expf(st[2 * k] - M) * inv : 0.f;
+  __syncthreads();
   const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-  accC[(long)b * C + c] = accCv + mm * g;
+
+  const int c = blockIdx.y * blockDim.x + threadIdx.x;
+  if (c < C) {
+    const float* part = ctx_part + (long)b * NCH * C + c;
+    float sum = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < NCH; ++k) sum += sm_w[k] * part[(long)k * C];
+    ctxpre_t[(long)b * C + c] = (bf16_t)sum;
+    const float accCv = accC[(long)b * C + c];
+    accC_used_t[(long)b * C + c] = (bf16_t)accCv;
+    // distraction over input content vectors (nats.py:545-546)
+    const float g = tanhf(Ucon[c] * sum + accCv * Wcon[c]);
+    ctxs_t[(long)b * C + c] = g;
+    hc_bf[(long)b * ldK1 + ctx_off + c] = (bf16_t)g;
+    accC[(long)b * C + c] = accCv + mm * g;
+  }
+
+  // the row's blocks split the s range between them
+  const int sper = (Ts + gridDim.y - 1) / gridDim.y;
+  const int s0 = blockIdx.y * sper;
+  const int s1 = min(Ts, s0 + sper);
+  for (int s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
+    const float al = alphas_t[(long)b * Ts + s] * sm_w[s / CH];
+    alphas_t[(long)b * Ts + s] = al;
+    const float av = accA[(long)b * Ts + s];
+    accA_used_t[(long)b * Ts + s] = av;
+    accA[(long)b * Ts + s] = av + mm * al;
+  }
+  if (blockIdx.y == 0) {
+    for (int i = threadIdx.x; i < A; i += blockDim.x) {
+      float ps = 0.f;
+      for (int k = 0; k < PS_KS; ++k) ps += ps_part[((long)k * 32 + b) * A + i];
+      pstate_t[(long)b * A + i] = ps;
+    }
+  }
 }
 
 // ---------------- GRU_1 forward (fused, small-K path) ----------------
@@ -384,11 +494,9 @@ __global__ void cond_gru1_step_pointwise(
 
 // ---------------- backward kernels ----------------
 
-// Fused per-step backward prologue: the GRU_1 pointwise, the independent
-// dctx passthrough (upstream readout grad + acc-chain, formerly its own
-// cond_dctx_dir launch), and the per-step re-zero of dot_buf (consumed by
-// last step's scatter/reduce before this kernel runs — stream order) all
-// share one grid-stride index space.
+// Fused per-step backward prologue: the GRU_1 pointwise and the
+// independent dctx passthrough (upstream readout grad + acc-chain, formerly
+// its own cond_dctx_dir launch) share one grid-stride index space.
 __global__ void cond_gru1_bwd_pointwise(
     const float* __restrict__ dh_carry,   // [B][H] (split-K half 0)
     const float* __restrict__ dh_carry2,  // [B][H] half 1 or null
@@ -405,24 +513,18 @@ __global__ void cond_gru1_bwd_pointwise(
     const float* __restrict__ dctxs_t,    // [B][C] or null (upstream)
     const float* __restrict__ daccC,      // [B][C] (pre-update, read)
     float* __restrict__ dctx_dir,         // [B][C] out
-    int C,
-    float* __restrict__ dot_buf,          // [B] (zeroed for this step)
-    int B, int H) {
+    int C, int B, int H) {
   const long total = (long)B * H;
-  const long total_all = total + (long)B * C + B;
+  const long total_all = total + (long)B * C;
   for (long idx2 = blockIdx.x * blockDim.x + threadIdx.x; idx2 < total_all;
        idx2 += (long)gridDim.x * blockDim.x) {
     if (idx2 >= total) {
       const long e = idx2 - total;
-      if (e < (long)B * C) {
-        const int b = e / C;
-        const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-        float v = mm * daccC[e];
-        if (dctxs_t != nullptr) v += dctxs_t[e];
-        dctx_dir[e] = v;
-      } else {
-        dot_buf[e - (long)B * C] = 0.f;
-      }
+      const int b = e / C;
+      const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
+      float v = mm * daccC[e];
+      if (dctxs_t != nullptr) v += dctxs_t[e];
+      dctx_dir[e] = v;
       continue;
     }
     const long idx = idx2;
@@ -624,9 +726,8 @@ __global__ __launch_bounds__(384) void cond_dh1_att_gemm(
   }
 }
 
-// attention backward, stage 1 (one WAVE per (b,s)): dalpha[s,b] =
-// ctx[s,b,:] . dctxpre[b,:] (+ acc-chain and upstream alpha grads) and the
-// softmax-backward dot partial, accumulated by atomics into dot_buf.
+// attention backward, stage 1 (one WAVE per (b,s)): dalpha[b,s] =
+// ctx[s,b,:] . dctxpre[b,:] (+ acc-chain and upstream alpha grads).
 __global__ __launch_bounds__(256) void cond_attn_bwd_dalpha(
     const bf16_t* __restrict__ ctx_bf,      // [Ts][B][C]
     const float* __restrict__ dctxpre_f32,  // [B][C]
@@ -634,8 +735,7 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_dalpha(
     const float* __restrict__ daccA,        // [B][Ts]
     const float* __restrict__ mask_t,       // [B] or null
     const float* __restrict__ dalphas_t,    // [B][Ts] or null
-    float* __restrict__ dal_buf,            // [Ts][B]
-    float* __restrict__ dot_buf,            // [B] (zeroed per step)
+    float* __restrict__ dal_buf,            // [B][Ts]
     int B, int Ts, int C) {
   const int b = blockIdx.x;
   const int wave = threadIdx.x / NATS_WAVE;
@@ -665,176 +765,142 @@ __global__ __launch_bounds__(256) void cond_attn_bwd_dalpha(
     const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
     dal += mm * daccA[(long)b * Ts + s];
     if (dalphas_t != nullptr) dal += dalphas_t[(long)b * Ts + s];
-    dal_buf[(long)s * B + b] = dal;
+    dal_buf[(long)b * Ts + s] = dal;
     // NOTE: the dot(alpha, dal) fold was MEASURED OUT here twice — a
     // per-s atomicAdd serializes ~Ts adds on one address (~120us/step,
     // round 1), and a per-BLOCK atomic tree still serialized Ts/4 adds
-    // per address (dalpha 9us -> 47.9us/call, prof_r2). The separate
-    // cond_attn_bwd_dot pass (~3us) stays.
+    // per address (dalpha 9us -> 47.9us/call, prof_r2). Every block of
+    // cond_attn_bwd_fused sums its row's dot itself instead.
   }
 }
 
-// softmax-backward dot: dot_buf[b] = sum_s alpha[b,s] * dal[s,b]
-__global__ __launch_bounds__(256) void cond_attn_bwd_dot(
-    const float* __restrict__ alphas_t, const float* __restrict__ dal_buf,
-    float* __restrict__ dot_buf, int B, int Ts) {
-  const int b = blockIdx.x;
-  float part = 0.f;
-  for (int s = threadIdx.x; s < Ts; s += blockDim.x)
-    part += alphas_t[(long)b * Ts + s] * dal_buf[(long)s * B + b];
-  const float S = block_reduce_sum(part);
-  if (threadIdx.x == 0) dot_buf[b] = S;
-}
-
-// attention backward, stage 2 (grid (B, ceil(Ts/256))): softmax backward,
-// per-(s,i) dpc into dpctx_acc + acc_alpha carry; tanh values stored to
-// pc_buf [B][A][Ts] (coalesced in s) for the stage-3 reduction, in fp32:
-// the reduction forms 1 - pc^2, which a bf16 copy of a saturated pc loses.
-__global__ __launch_bounds__(256) void cond_attn_bwd_scatter(
+// attention backward, stage 2 (one block per (b, s-chunk), all of A in the
+// block): the softmax-backward dot, the per-(s, i) tanh backward into
+// dpctx_acc and the acc_alpha carry, and the chunk's column sums for
+// dpstate / dD_wei / dU_att / dc_att, in one pass. The tanh values and
+// their gradients go from the (s, i) loop to the column sums through an
+// LDS tile, in fp32: 1 - pc^2 of a saturated pc has no relative precision
+// left in a bf16 copy.
+__global__ __launch_bounds__(ATT_THREADS) void cond_attn_bwd_fused(
     const float* __restrict__ alphas_t,     // [B][Ts]
-    const float* __restrict__ dal_buf,      // [Ts][B]
-    const float* __restrict__ dot_buf,      // [B]
+    const float* __restrict__ dal_buf,      // [B][Ts]
     const float* __restrict__ pctx,         // [Ts][B][A]
     const float* __restrict__ pstate_t,     // [B][A]
     const float* __restrict__ accA_used_t,  // [B][Ts]
     const float* __restrict__ Dwei, const float* __restrict__ Uatt,
-    float* __restrict__ daccA,              // [B][Ts] (+=, atomic)
+    float* __restrict__ daccA,              // [B][Ts] (+=)
     float* __restrict__ dpctx_acc,          // [Ts][B][A] (+=)
-    float* __restrict__ pc_buf,             // [B][A][Tpad8]
-    int B, int Ts, int A, int Tpad8) {
-  // grid (B, s-chunks, A-chunks): the un-chunked variant ran only
-  // B * Ts/256 blocks (2 waves/CU at the CNN/DM shape) and was
-  // latency-bound on its serial per-A float4 RMW chain.
+    float* __restrict__ dpstate_t,          // [B][A] (one atomic per block)
+    float* __restrict__ gslot,              // [B][NCH][2A+1] (+=, own slot)
+    int B, int Ts, int A, int CH, int lps) {
+  // [3A] ps|Dwei|Uatt, then the [CH][A] dpc and pc tiles
+  extern __shared__ __attribute__((aligned(16))) float sm_att[];
+  __shared__ float sm_de[ATT_CH_MAX];
+  __shared__ float sm_au[ATT_CH_MAX];
+  const int A4 = (A + 3) & ~3;  // keeps the tiles 16 B aligned
+  const float* sm_ps = sm_att;
+  const float* sm_dw = sm_att + A;
+  const float* sm_ua = sm_att + 2 * A;
+  float* t_dpc = sm_att + 3 * A4;
+  float* t_pc = t_dpc + (long)CH * A;
   const int b = blockIdx.x;
-  const int s = blockIdx.y * blockDim.x + threadIdx.x;
-  if (s >= Ts) return;
-  const int ACH = gridDim.z;
-  const int chunkA = ((A + ACH - 1) / ACH + 3) & ~3;  // 16B-aligned splits
-  const int ibeg = blockIdx.z * chunkA;
-  const int iend = min(A, ibeg + chunkA);
-  if (ibeg >= iend) return;
-  const float al = alphas_t[(long)b * Ts + s];
-  const float de = al * (dal_buf[(long)s * B + b] - dot_buf[b]);
-  const float accAu = accA_used_t[(long)b * Ts + s];
-  const float* prow = pctx + ((long)s * B + b) * A;
-  const float* srow = pstate_t + (long)b * A;
-  float* dprow = dpctx_acc + ((long)s * B + b) * A;
-  float daccA_add = 0.f;
-  const int A4 = (A % 4 == 0) ? iend : ibeg;  // f32x4 needs A % 4 == 0
-  int i = ibeg;
-  for (; i < A4; i += 4) {
-    const float4 p = *(const float4*)(prow + i);
-    const float4 st = *(const float4*)(srow + i);
-    const float4 dw = *(const float4*)(Dwei + i);
-    const float4 ua = *(const float4*)(Uatt + i);
-    float4 dpv = *(const float4*)(dprow + i);
-    const float pc0 = tanhf(p.x + st.x + accAu * dw.x);
-    const float pc1 = tanhf(p.y + st.y + accAu * dw.y);
-    const float pc2 = tanhf(p.z + st.z + accAu * dw.z);
-    const float pc3 = tanhf(p.w + st.w + accAu * dw.w);
-    const float d0 = de * (1.f - pc0 * pc0) * ua.x;
-    const float d1 = de * (1.f - pc1 * pc1) * ua.y;
-    const float d2 = de * (1.f - pc2 * pc2) * ua.z;
-    const float d3 = de * (1.f - pc3 * pc3) * ua.w;
-    dpv.x += d0;
-    dpv.y += d1;
-    dpv.z += d2;
-    dpv.w += d3;
-    *(float4*)(dprow + i) = dpv;
-    daccA_add += d0 * dw.x + d1 * dw.y + d2 * dw.z + d3 * dw.w;
-    pc_buf[((long)b * A + i) * Tpad8 + s] = pc0;
-    pc_buf[((long)b * A + i + 1) * Tpad8 + s] = pc1;
-    pc_buf[((long)b * A + i + 2) * Tpad8 + s] = pc2;
-    pc_buf[((long)b * A + i + 3) * Tpad8 + s] = pc3;
-  }
-  for (; i < iend; ++i) {
-    const float pc = tanhf(prow[i] + srow[i] + accAu * Dwei[i]);
-    const float dpc = de * (1.f - pc * pc) * Uatt[i];
-    dprow[i] += dpc;
-    daccA_add += dpc * Dwei[i];
-    pc_buf[((long)b * A + i) * Tpad8 + s] = pc;
-  }
-  if (ACH == 1) {
-    daccA[(long)b * Ts + s] += daccA_add;
-  } else {
-    atomicAdd(daccA + (long)b * Ts + s, daccA_add);
-  }
-}
+  const int NCH = gridDim.y;
+  const int sbeg = blockIdx.y * CH;
+  const int n = min(CH, Ts - sbeg);
+  attn_stage_vectors(sm_att, pstate_t, 1, 0, b, Dwei, Uatt, A);
 
-// attention backward, stage 3 (grid (b, s-chunk)): reduce over an
-// s-range of the contiguous pc_buf rows -> dpstate / dD_wei / dU_att /
-// dc_att by atomic combine. de and accA_used for the range staged in LDS.
-__global__ __launch_bounds__(256) void cond_attn_bwd_reduce(
-    const float* __restrict__ alphas_t,     // [B][Ts]
-    const float* __restrict__ dal_buf,      // [Ts][B]
-    const float* __restrict__ dot_buf,      // [B]
-    const float* __restrict__ accA_used_t,  // [B][Ts]
-    const float* __restrict__ pc_buf,       // [B][A][Tpad8]
-    const float* __restrict__ Uatt,
-    float* __restrict__ dpstate_t,          // [B][A]
-    float* __restrict__ gdDwei,             // [A] (atomic)
-    float* __restrict__ gdUatt,             // [A] (atomic)
-    float* __restrict__ gdcatt,             // [1] (atomic)
-    int B, int Ts, int A, int Apad, int Tpad8, int SCH) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int chunk = (Ts + SCH - 1) / SCH;
-  float* sm_de = (float*)smem_raw;      // [chunk]
-  float* sm_au = sm_de + chunk;         // [chunk]
-  const int b = blockIdx.x;
-  const int sbeg = blockIdx.y * chunk;
-  const int send = min(Ts, sbeg + chunk);
-  const float dot = dot_buf[b];
+  // dot = sum_s alpha * dal over the WHOLE row, summed in a fixed order:
+  // every block of the row gets the same bits
+  float part = 0.f;
+  for (int s = threadIdx.x; s < Ts; s += blockDim.x)
+    part += alphas_t[(long)b * Ts + s] * dal_buf[(long)b * Ts + s];
+  const float dot = block_reduce_sum(part);  // also orders the staging
+
   float dc = 0.f;
-  for (int s = sbeg + threadIdx.x; s < send; s += blockDim.x) {
-    const float de = alphas_t[(long)b * Ts + s] *
-                     (dal_buf[(long)s * B + b] - dot);
-    sm_de[s - sbeg] = de;
-    sm_au[s - sbeg] = accA_used_t[(long)b * Ts + s];
-    dc += de;
-  }
-  const float dc_blk = block_reduce_sum(dc);  // also orders sm_de / sm_au
-  if (threadIdx.x == 0) atomicAdd(gdcatt, dc_blk);
-  for (int i = threadIdx.x; i < A; i += blockDim.x) {
-    const float* prow = pc_buf + ((long)b * A + i) * Tpad8;
-    const float ua = Uatt[i];
-    float sps = 0.f, sdw = 0.f, sua = 0.f;
-    int s = sbeg;
-    const int a8beg = (sbeg + 7) & ~7;
-    const int a8end = send & ~7;
-    for (; s < min(a8beg, send); ++s) {
-      const float pc = prow[s];
-      const float de = sm_de[s - sbeg];
-      const float dpc = de * (1.f - pc * pc) * ua;
-      sps += dpc;
-      sdw += dpc * sm_au[s - sbeg];
-      sua += de * pc;
+  if (threadIdx.x < NATS_WAVE) {
+    const int ls = threadIdx.x;
+    float de = 0.f, au = 0.f;
+    if (ls < n) {
+      const long bs = (long)b * Ts + sbeg + ls;
+      de = alphas_t[bs] * (dal_buf[bs] - dot);
+      au = accA_used_t[bs];
     }
-    for (; s + 8 <= a8end; s += 8) {
-      const float4 p0 = *(const float4*)(prow + s);
-      const float4 p1 = *(const float4*)(prow + s + 4);
-      const float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+    sm_de[ls] = de;
+    sm_au[ls] = au;
+    dc = de;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float pc = pv[k];
-        const float de = sm_de[s + k - sbeg];
-        const float dpc = de * (1.f - pc * pc) * ua;
-        sps += dpc;
-        sdw += dpc * sm_au[s + k - sbeg];
-        sua += de * pc;
+    for (int off = NATS_WAVE / 2; off > 0; off >>= 1)
+      dc += __shfl_xor(dc, off);
+  }
+  __syncthreads();
+
+  const int gl = threadIdx.x % lps;
+  const int ngrp = ATT_THREADS / lps;
+  for (int ls = threadIdx.x / lps; ls < n; ls += ngrp) {
+    const int s = sbeg + ls;
+    const float de = sm_de[ls];
+    const float accAu = sm_au[ls];
+    const float* prow = pctx + ((long)s * B + b) * A;
+    float* dprow = dpctx_acc + ((long)s * B + b) * A;
+    float* drow = t_dpc + (long)ls * A;
+    float* crow = t_pc + (long)ls * A;
+    float dacc = 0.f;
+    if (A % 4 == 0) {
+      for (int i = gl * 4; i < A; i += lps * 4) {
+        const float4 p = *(const float4*)(prow + i);
+        const float4 st = *(const float4*)(sm_ps + i);
+        const float4 dw = *(const float4*)(sm_dw + i);
+        const float4 ua = *(const float4*)(sm_ua + i);
+        float4 dpv = *(const float4*)(dprow + i);
+        float4 pc, d;
+        pc.x = tanhf(p.x + st.x + accAu * dw.x);
+        pc.y = tanhf(p.y + st.y + accAu * dw.y);
+        pc.z = tanhf(p.z + st.z + accAu * dw.z);
+        pc.w = tanhf(p.w + st.w + accAu * dw.w);
+        d.x = de * (1.f - pc.x * pc.x) * ua.x;
+        d.y = de * (1.f - pc.y * pc.y) * ua.y;
+        d.z = de * (1.f - pc.z * pc.z) * ua.z;
+        d.w = de * (1.f - pc.w * pc.w) * ua.w;
+        dpv.x += d.x;
+        dpv.y += d.y;
+        dpv.z += d.z;
+        dpv.w += d.w;
+        *(float4*)(dprow + i) = dpv;
+        dacc += d.x * dw.x + d.y * dw.y + d.z * dw.z + d.w * dw.w;
+        *(float4*)(drow + i) = d;
+        *(float4*)(crow + i) = pc;
+      }
+    } else {
+      for (int i = gl; i < A; i += lps) {
+        const float pc = tanhf(prow[i] + sm_ps[i] + accAu * sm_dw[i]);
+        const float d = de * (1.f - pc * pc) * sm_ua[i];
+        dprow[i] += d;
+        dacc += d * sm_dw[i];
+        drow[i] = d;
+        crow[i] = pc;
       }
     }
-    for (; s < send; ++s) {
-      const float pc = prow[s];
-      const float de = sm_de[s - sbeg];
-      const float dpc = de * (1.f - pc * pc) * ua;
-      sps += dpc;
-      sdw += dpc * sm_au[s - sbeg];
-      sua += de * pc;
+    for (int off = lps / 2; off > 0; off >>= 1) dacc += __shfl_xor(dacc, off);
+    // the block owns all of A for its s: plain +=
+    if (gl == 0) daccA[(long)b * Ts + s] += dacc;
+  }
+  __syncthreads();
+
+  // column sums over the chunk: thread i owns column i
+  float* slot = gslot + ((long)b * NCH + blockIdx.y) * (2 * A + 1);
+  for (int i = threadIdx.x; i < A; i += blockDim.x) {
+    float sps = 0.f, sdw = 0.f, sua = 0.f;
+    for (int ls = 0; ls < n; ++ls) {
+      const float d = t_dpc[(long)ls * A + i];
+      sps += d;
+      sdw += d * sm_au[ls];
+      sua += sm_de[ls] * t_pc[(long)ls * A + i];
     }
     atomicAdd(&dpstate_t[(long)b * A + i], sps);
-    atomicAdd(&gdDwei[i], sdw);
-    atomicAdd(&gdUatt[i], sua);
+    slot[i] += sdw;
+    slot[A + i] += sua;
   }
+  if (threadIdx.x == 0) slot[2 * A] += dc;
 }
 
 }  // namespace
@@ -887,11 +953,16 @@ std::vector<torch::Tensor> cond_gru_fwd(
   const int GRU2_KS = 4;
   auto gru2_part = torch::empty({GRU2_KS, 3, 32, Hpad}, optsF);
   auto hc_bf = torch::zeros({32, K1}, optsB);
-  auto e_buf = torch::zeros({Ts, B}, optsF);  // escore accumulates into it
   const int PS_KS = 4;
   auto ps_part = torch::empty({PS_KS, 32, A}, optsF);
-  auto ctxpre_f32 = torch::zeros({B, C}, optsF);  // gate_fwd re-zeroes
-  const int SCH = std::max(1, std::min(8, Ts / 64));
+  // attention chunking (rule at attn_chunk_len): every (b, chunk) block
+  // writes its own statistics pair and partial context with plain stores,
+  // so neither buffer needs zeroing
+  const int CH = attn_chunk_len(B, Ts);
+  const int NCH = cdiv(Ts, CH);
+  const int lps = attn_lanes_per_s(CH);
+  auto att_stats = torch::empty({B, NCH, 2}, optsF);
+  auto ctx_part = torch::empty({B, NCH, C}, optsF);
   auto init_f = init_state.contiguous().to(torch::kFloat32);
   h2bf[0].slice(0, 0, B).slice(1, 0, H).copy_(init_f.to(torch::kBFloat16));
 
@@ -935,39 +1006,34 @@ std::vector<torch::Tensor> cond_gru_fwd(
                          (bf16_t*)saved2.data_ptr() + (long)t * B * 3 * H, B,
                          H, Hpad);
     }
-    // 2) pstate = h1 @ W_att (split-K partials; combined in softmax)
+    // 2) pstate = h1 @ W_att (split-K partials; summed by the consumers)
     hipLaunchKernelGGL(cond_small_gemm_bt, dim3(2, Apad16 / 16, PS_KS),
                        dim3(64), 0, stream, (const bf16_t*)hc_bf.data_ptr(),
                        (const bf16_t*)WattPk.data_ptr(),
                        ps_part.data_ptr<float>(), B, A, K1,
                        (int)WattPk.size(1));
-    // 3) attention scores (s- and A-parallel) + softmax + acc_alpha
-    hipLaunchKernelGGL(cond_attn_escore,
-                       dim3(B, cdiv(Ts, 256), A >= 16 ? 4 : 1), dim3(256),
+    // 3) attention pass 1, one block per (b, s-chunk): e-scores,
+    // chunk-local softmax statistics, unnormalised partial context
+    hipLaunchKernelGGL(cond_attn_fwd_chunk, dim3(B, NCH), dim3(ATT_THREADS),
                        3 * A * sizeof(float), stream, pctx.data_ptr<float>(),
                        ps_part.data_ptr<float>(), PS_KS,
                        accA.data_ptr<float>(), Dwei.data_ptr<float>(),
                        Uatt.data_ptr<float>(), catt.data_ptr<float>(),
-                       e_buf.data_ptr<float>(), B, Ts, A);
-    // 1024 threads: the kernel runs only B blocks (latency-bound) —
-    // wider blocks quarter the serial passes over Ts
-    hipLaunchKernelGGL(cond_attn_softmax, dim3(B), dim3(1024), 0, stream,
+                       cmask_p, (const bf16_t*)ctx_bf.data_ptr(),
+                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
+                       att_stats.data_ptr<float>(),
+                       ctx_part.data_ptr<float>(), B, Ts, A, C, CH, lps);
+    // 4) attention pass 2: global softmax statistics, combined context,
+    // gate + acc_ctx, normalised alphas + acc_alpha, combined pstate
+    hipLaunchKernelGGL(cond_attn_combine_gate, dim3(B, cdiv(C, ATT_THREADS)),
+                       dim3(ATT_THREADS), NCH * sizeof(float), stream,
+                       att_stats.data_ptr<float>(),
+                       ctx_part.data_ptr<float>(), NCH, CH,
+                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
                        accA.data_ptr<float>(),
                        accA_used.data_ptr<float>() + (long)t * B * Ts,
-                       cmask_p, mt, e_buf.data_ptr<float>(),
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
                        ps_part.data_ptr<float>(), PS_KS,
-                       pstate_all.data_ptr<float>() + (long)t * B * A, A, B,
-                       Ts);
-    // 4) weighted context (s-chunked partials) + gate + acc_ctx
-    // (ctxpre_f32 arrives zeroed: gate_fwd re-zeroes it after reading)
-    hipLaunchKernelGGL(cond_attn_ctx_partial,
-                       dim3(B, cdiv(C, 256), SCH), dim3(256), 0, stream,
-                       (const bf16_t*)ctx_bf.data_ptr(),
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       ctxpre_f32.data_ptr<float>(), B, Ts, C, SCH);
-    hipLaunchKernelGGL(cond_attn_gate_fwd, dim3(B, cdiv(C, 256)), dim3(256),
-                       0, stream, ctxpre_f32.data_ptr<float>(),
+                       pstate_all.data_ptr<float>() + (long)t * B * A, A, Ts,
                        Ucon.data_ptr<float>(), Wcon.data_ptr<float>(),
                        accC.data_ptr<float>(),
                        (bf16_t*)accC_used.data_ptr() + (long)t * B * C,
@@ -1041,11 +1107,21 @@ std::vector<torch::Tensor> cond_gru_bwd(
   auto dctxpre_all = torch::empty({T, B, C}, optsB);
   auto gdUcon = torch::zeros({C}, optsF);
   auto gdWcon = torch::zeros({C}, optsF);
-  auto dpstate_all = torch::zeros({T, B, A}, optsF);  // reduce atomic-adds
+  auto dpstate_all = torch::zeros({T, B, A}, optsF);  // per-chunk atomics
   auto dpctx_acc = torch::zeros({Ts, B, A}, optsF);
-  auto gdDwei = torch::zeros({A}, optsF);
-  auto gdUatt = torch::zeros({A}, optsF);
-  auto gdcatt = torch::zeros({1}, optsF);
+  // attention chunking as in the forward, the chunk further capped so the
+  // two [CH][A] fp32 tiles fit 60 KB of LDS next to the staged vectors
+  const int A4 = (A + 3) & ~3;
+  const int lds_floats = 60 * 1024 / (int)sizeof(float);
+  TORCH_CHECK(3 * A4 + 2 * 8 * A <= lds_floats,
+              "cond_gru_bwd: dim_att too large for the attention tiles");
+  const int CH = std::min(attn_chunk_len(B, Ts),
+                          ((lds_floats - 3 * A4) / (2 * A)) & ~7);
+  const int NCH = cdiv(Ts, CH);
+  const int lps = attn_lanes_per_s(CH);
+  // dD_wei | dU_att | dc_att: one slot per (b, chunk) block, accumulated
+  // over the time loop with plain adds, summed once after it
+  auto gslot = torch::zeros({B * NCH, 2 * A + 1}, optsF);
 
   auto dh_carry = torch::zeros({2, B, H}, optsF);
   auto dh1_buf = torch::zeros({B, H}, optsF);
@@ -1057,11 +1133,7 @@ std::vector<torch::Tensor> cond_gru_bwd(
                                    : torch::zeros({B, Ts}, optsF);
   auto daccC = daccC_f.has_value() ? daccC_f->contiguous().to(torch::kFloat32)
                                    : torch::zeros({B, C}, optsF);
-  auto dal_buf = torch::empty({Ts, B}, optsF);
-  auto dot_buf = torch::empty({B}, optsF);
-  const int Tpad8 = (Ts + 7) / 8 * 8;
-  auto pc_buf = torch::empty({B, A, Tpad8}, optsF);
-  const int Apad = Apad32;
+  auto dal_buf = torch::empty({B, Ts}, optsF);
   auto dstep1 = torch::zeros({32, K3Hpad}, optsB);
   auto dstepC = torch::zeros({32, K3Hpad}, optsB);
   auto dstep2 = torch::zeros({32, K3Hpad}, optsB);
@@ -1076,14 +1148,14 @@ std::vector<torch::Tensor> cond_gru_bwd(
   auto dh2_c = dh2_all.contiguous().to(torch::kFloat32);
   const int pwH = (int)std::min<long>(512, (((long)B * H) + 255) / 256);
   const int pwHC =
-      (int)std::min<long>(512, (((long)B * (H + C) + B) + 255) / 256);
+      (int)std::min<long>(512, (((long)B * (H + C)) + 255) / 256);
 
   for (int t = T - 1; t >= 0; --t) {
     const float* mt = mask_all ? mask_all + (long)t * B : nullptr;
     const float* h2prev =
         (t == 0) ? init_f.data_ptr<float>()
                  : h2_all.data_ptr<float>() + (long)(t - 1) * B * H;
-    // b1 (fused): GRU_1 pointwise + dctx passthrough + dot_buf re-zero
+    // b1 (fused): GRU_1 pointwise + dctx passthrough
     hipLaunchKernelGGL(cond_gru1_bwd_pointwise, dim3(pwHC), dim3(256), 0,
                        stream, dh_carry.data_ptr<float>(),
                        dh_carry.data_ptr<float>() + (long)B * H,
@@ -1096,7 +1168,7 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        (bf16_t*)dpre1_all.data_ptr() + (long)t * B * 4 * H,
                        dctxs_p ? dctxs_p + (long)t * B * C : nullptr,
                        daccC.data_ptr<float>(), dctx_dir.data_ptr<float>(), C,
-                       dot_buf.data_ptr<float>(), B, H);
+                       B, H);
     // b2+b3+b4 fused launch: dh1 = ddirect_h1 + dstep1 @ [U_1|Ux_1]^T and
     // the dctx GEMM with the distraction-gate backward applied in the
     // epilogue (the former separate cond_gate_bwd pass)
@@ -1117,10 +1189,9 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        (const bf16_t*)accC_used.data_ptr() + (long)t * B * C,
                        gdUcon.data_ptr<float>(), gdWcon.data_ptr<float>(),
                        B);
-    // b5: attention backward — wave-per-(b,s) dalpha with the softmax-bwd
-    // dot folded in (block tree + one atomic per block), then the
-    // (b,s)-parallel scatter (dpctx/daccA/pc_buf) and the per-(b,i)
-    // s-contiguous reduce for dpstate/dD_wei/dU_att/dc_att
+    // b5: attention backward — wave-per-(b,s) dalpha, then one pass per
+    // (b, s-chunk) block: softmax-bwd dot, dpctx/daccA, and the column
+    // sums for dpstate/dD_wei/dU_att/dc_att through an LDS tile
     hipLaunchKernelGGL(cond_attn_bwd_dalpha, dim3(B, cdiv(Ts, 4)),
                        dim3(256), 0, stream,
                        (const bf16_t*)ctx_bf.data_ptr(),
@@ -1128,35 +1199,17 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        alphas_all.data_ptr<float>() + (long)t * B * Ts,
                        daccA.data_ptr<float>(), mt,
                        dalpha_p ? dalpha_p + (long)t * B * Ts : nullptr,
-                       dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),
-                       B, Ts, C);
-    hipLaunchKernelGGL(cond_attn_bwd_dot, dim3(B), dim3(256), 0, stream,
+                       dal_buf.data_ptr<float>(), B, Ts, C);
+    hipLaunchKernelGGL(cond_attn_bwd_fused, dim3(B, NCH), dim3(ATT_THREADS),
+                       (3 * A4 + 2 * CH * A) * sizeof(float), stream,
                        alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),
-                       B, Ts);
-    hipLaunchKernelGGL(cond_attn_bwd_scatter,
-                       dim3(B, cdiv(Ts, 256), A >= 32 ? 8 : (A >= 16 ? 4 : 1)),
-                       dim3(256), 0, stream,
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),
-                       pctx.data_ptr<float>(),
+                       dal_buf.data_ptr<float>(), pctx.data_ptr<float>(),
                        pstate_all.data_ptr<float>() + (long)t * B * A,
                        accA_used.data_ptr<float>() + (long)t * B * Ts,
                        Dwei.data_ptr<float>(), Uatt.data_ptr<float>(),
                        daccA.data_ptr<float>(), dpctx_acc.data_ptr<float>(),
-                       pc_buf.data_ptr<float>(), B, Ts, A, Tpad8);
-    const int RSCH = std::max(1, std::min(12, Ts / 64));
-    hipLaunchKernelGGL(cond_attn_bwd_reduce, dim3(B, RSCH), dim3(256),
-                       2 * ((Ts + RSCH - 1) / RSCH) * sizeof(float), stream,
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       dal_buf.data_ptr<float>(), dot_buf.data_ptr<float>(),
-                       accA_used.data_ptr<float>() + (long)t * B * Ts,
-                       pc_buf.data_ptr<float>(),
-                       Uatt.data_ptr<float>(),
                        dpstate_all.data_ptr<float>() + (long)t * B * A,
-                       gdDwei.data_ptr<float>(), gdUatt.data_ptr<float>(),
-                       gdcatt.data_ptr<float>(), B, Ts, A, Apad32, Tpad8,
-                       RSCH);
+                       gslot.data_ptr<float>(), B, Ts, A, CH, lps);
     // b6a: dh1 += dpstate @ W_att^T — A fragments converted from the
     // fp32 dpstate in-register (no cond_dpstate_cast pass)
     hipLaunchKernelGGL(cond_dh1_att_gemm, dim3(ngrpH), dim3(384), 0, stream,
@@ -1183,6 +1236,10 @@ std::vector<torch::Tensor> cond_gru_bwd(
   }
   HIP_CHECK(hipGetLastError());
   auto dh_carry_sum = dh_carry[0] + dh_carry[1];
+  auto gsum = gslot.sum(0);
+  auto gdDwei = gsum.slice(0, 0, A).contiguous();
+  auto gdUatt = gsum.slice(0, A, 2 * A).contiguous();
+  auto gdcatt = gsum.slice(0, 2 * A, 2 * A + 1).contiguous();
   return {dpre1_all, dpre2_all, dctxpre_all, gdUcon, dpstate_all,
           dpctx_acc, gdDwei, gdUatt, gdcatt, dh_carry_sum, daccC, daccA,
           gdWcon};

@@ -15,6 +15,7 @@ SOURCES = [
     os.path.join(HERE, "bind.cpp"),
     os.path.join(HERE, "gru_scan.hip"),
     os.path.join(HERE, "cond_gru.hip"),
+    os.path.join(HERE, "barrier_bench.hip"),
     os.path.join(HERE, "softmax_ce.hip"),
     os.path.join(HERE, "mfma_test.hip"),
     os.path.join(HERE, "optim.hip"),

@@ -3,8 +3,11 @@
 // Implements the reference's gru_cond_layer step (nats.py:498-572; kernel
 // rows K10-K16 in SURVEY §2.4) as five fused stages per timestep driven
 // by a C++ time loop (no python in the scan):
-//   1. GRU_2          — reuses nats_gru_step_fwd (identical cell math)
-//   2. pstate GEMM    — h1 @ W_att (small MFMA GEMM, cond_small_gemm_bt)
+//   1. GRU_2          — the encoder cell (gru_kernels.h): nats_gru_step_fwd,
+//                       or nats_gru2_gemm_splitk + nats_gru2_step_pointwise
+//                       when Hpad >= 1024
+//   2. pstate GEMM    — h1 @ W_att (cond_small_gemm_bt, split-K partials
+//                       summed by stages 3 and 4)
 //   3. attention 1    — cond_attn_fwd_chunk, one WG per (batch row,
 //                       s-chunk): e-scores + distraction-over-weights,
 //                       chunk-local masked softmax statistics (online
@@ -14,10 +17,17 @@
 //                       vectors + acc_ctx update, normalised alphas +
 //                       acc_alpha update
 //   5. GRU_1          — 4-output-group MFMA ([h1|ctx] packed operand) +
-//                       gates/mask pointwise
-// The attention backward is cond_attn_bwd_dalpha (one wave per (b, s)
-// context row) and cond_attn_bwd_fused (one WG per (b, s-chunk): softmax
-// backward, tanh backward into dpctx/acc_alpha, column sums through LDS).
+//                       gates/mask: cond_gru1_step_fwd, or
+//                       cond_gru1_gemm_splitk + cond_gru1_step_pointwise
+//                       when K1 >= 2048 (one MFMA phase, one finish)
+// Backward, per step in reverse: cond_gru1_bwd_pointwise (GRU_1 gates +
+// dctx passthrough), cond_bwd_gemm_dual_gate (dh1 and the dctx GEMM with
+// the gate backward in its epilogue), cond_attn_bwd_dalpha (one wave per
+// (b, s) context row), cond_attn_bwd_fused (one WG per (b, s-chunk):
+// softmax backward, tanh backward into dpctx/acc_alpha, column sums through
+// LDS), cond_dh1_att_gemm, nats_gru_step_bwd_pointwise (GRU_2 gates) and
+// cond_dh_carry_gemm_split. The recurrent GEMMs share row_gemm
+// (gru_kernels.h).
 // The backward pass is the exact reverse chain with the running-sum
 // accumulators' (acc_ctx/acc_alpha) gradients threaded backwards
 // (SURVEY §7 "hard parts" (ii)); weight gradients that factor over time
@@ -71,13 +81,10 @@ __global__ void cond_small_gemm_bt(const bf16_t* __restrict__ A,
                                    int ldK, int Kpad) {
   const int m0 = blockIdx.x * 16;
   const int n0 = blockIdx.y * 16;
-  const int KS = gridDim.z;
-  const int kchunk = ((Kpad / KS + 31) / 32) * 32;
-  const int kbeg = min(Kpad, (int)blockIdx.z * kchunk);
-  const int kend = min(Kpad, kbeg + kchunk);
+  const KRange k = k_part(KRange{0, Kpad}, gridDim.z, blockIdx.z);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   // NB: Bt's row stride is Kpad (the packed weight width), NOT ldK.
-  NATS_MFMA_KLOOP(acc, A, m0, ldK, Bt, n0, Kpad, kbeg, kend);
+  NATS_MFMA_KLOOP(acc, A, m0, ldK, Bt, n0, Kpad, k.beg, k.end);
   const int lane = threadIdx.x & (NATS_WAVE - 1);
   const int col = n0 + (lane & 15);
   const int rbase = m0 + (lane >> 4) * 4;
@@ -359,7 +366,40 @@ __global__ __launch_bounds__(ATT_THREADS) void cond_attn_combine_gate(
 // g0 = r2 (K = h1|ctx), g1 = u2 (K = h1|ctx), g2 = pxa (h1@Ux_1),
 // g3 = pxb (ctx@Wx_1) — K-selectivity comes from zero blocks in W1pk.
 // K is split across wave pairs (K1 is ~3H — the serial chain at 8 waves
-// measured 34 us/launch, latency-bound).
+// measured 34 us/launch, latency-bound). Split-K block ksb of KS takes K
+// parts 2*ksb and 2*ksb+1 of 2*KS; the fused kernel is KS = 1.
+__device__ __forceinline__ void gru1_mfma_phase(
+    float (*pre)[2][32][JB + 1],  // [4][2][32][JB+1] out (caller barriers)
+    const bf16_t* hc_bf, const bf16_t* W1pk, int K1, int wg, int ksb, int KS) {
+  const int wave = threadIdx.x / NATS_WAVE;
+  const int m = wave / 8;
+  const int g = (wave % 8) / 2;
+  const int ks = wave % 2;
+  const KRange k = k_part(KRange{0, K1}, 2 * KS, 2 * ksb + ks);
+
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const bf16_t* brow = W1pk + (long)(wg * 4 + g) * JB * K1;
+  NATS_MFMA_KLOOP(acc, hc_bf, 16 * m, K1, brow, 0, K1, k.beg, k.end);
+  store_cd_lds(pre[g][ks], acc, 16 * m);
+}
+
+// GRU_1 finish of element (b, j) from the four summed preactivations:
+// cell, h2 (fp32 + bf16 operand copy) and saved1 = (r2, u2, pxa, hbar).
+__device__ __forceinline__ void gru1_fwd_finish(
+    float p0, float p1, float pxa, float pxb, const float* h1_t,
+    const float* b1, const float* bx1, const float* mask_t, float* h2_t,
+    bf16_t* h2bf_out, int ld_h2bf, float* saved1_t, int H, int b, int j) {
+  const long bj = (long)b * H + j;
+  const GruCellFwd o = gru_cell_fwd(p0 + b1[j], p1 + b1[H + j], pxa + bx1[j],
+                                    pxb, h1_t[bj], mask_t, b);
+  h2_t[bj] = o.hnew;
+  h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
+  saved1_t[(long)b * 4 * H + j] = o.r;
+  saved1_t[(long)b * 4 * H + H + j] = o.u;
+  saved1_t[(long)b * 4 * H + 2 * H + j] = pxa;
+  saved1_t[(long)b * 4 * H + 3 * H + j] = o.hbar;
+}
+
 __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
     const bf16_t* __restrict__ hc_bf,  // [32][K1] = [h1 | ctx_t] bf16
     const float* __restrict__ h1_t,    // [B][H] fp32
@@ -373,21 +413,8 @@ __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
     float* __restrict__ saved1_t,      // [B][4H] (r2,u2,pxa,hbar)
     int B, int H, int K1) {
   __shared__ float pre[4][2][32][JB + 1];
-
-  const int wg = blockIdx.x;
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 8;
-  const int g = (wave % 8) / 2;
-  const int ks = wave % 2;
-  const int j0 = wg * JB;
-  const int khalf = ((K1 / 2 + 31) / 32) * 32;
-  const int kbeg = ks * khalf;
-  const int kend = min(K1, (ks + 1) * khalf);
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const bf16_t* brow = W1pk + (long)(wg * 4 + g) * JB * K1;
-  NATS_MFMA_KLOOP(acc, hc_bf, 16 * m, K1, brow, 0, K1, kbeg, kend);
-  store_cd_lds(pre[g][ks], acc, 16 * m);
+  const int j0 = blockIdx.x * JB;
+  gru1_mfma_phase(pre, hc_bf, W1pk, K1, blockIdx.x, 0, 1);
   __syncthreads();
 
   for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
@@ -395,18 +422,11 @@ __global__ __launch_bounds__(1024) void cond_gru1_step_fwd(
     const int c = idx % JB;
     const int j = j0 + c;
     if (j >= H) continue;
-    const float pxa = pre[2][0][b][c] + pre[2][1][b][c];
-    const float pxb = pre[3][0][b][c] + pre[3][1][b][c];
-    const GruCellFwd o = gru_cell_fwd(
-        pre[0][0][b][c] + pre[0][1][b][c] + b1[j],
-        pre[1][0][b][c] + pre[1][1][b][c] + b1[H + j], pxa + bx1[j], pxb,
-        h1_t[(long)b * H + j], mask_t, b);
-    h2_t[(long)b * H + j] = o.hnew;
-    h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
-    saved1_t[(long)b * 4 * H + j] = o.r;
-    saved1_t[(long)b * 4 * H + H + j] = o.u;
-    saved1_t[(long)b * 4 * H + 2 * H + j] = pxa;
-    saved1_t[(long)b * 4 * H + 3 * H + j] = o.hbar;
+    gru1_fwd_finish(pre[0][0][b][c] + pre[0][1][b][c],
+                    pre[1][0][b][c] + pre[1][1][b][c],
+                    pre[2][0][b][c] + pre[2][1][b][c],
+                    pre[3][0][b][c] + pre[3][1][b][c], h1_t, b1, bx1, mask_t,
+                    h2_t, h2bf_out, ld_h2bf, saved1_t, H, b, j);
   }
 }
 
@@ -423,25 +443,9 @@ __global__ __launch_bounds__(1024) void cond_gru1_gemm_splitk(
     float* __restrict__ part,          // [KS][4][32][Hpad]
     int H, int K1, int Hpad) {
   __shared__ float pre[4][2][32][JB + 1];
-
-  const int wg = blockIdx.x;
   const int ksb = blockIdx.y;
-  const int KS = gridDim.y;
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 8;
-  const int g = (wave % 8) / 2;
-  const int ks = wave % 2;
-  const int j0 = wg * JB;
-  const int nchunk = 2 * KS;
-  const int kchunk = ((K1 / nchunk + 31) / 32) * 32;
-  const int kidx = 2 * ksb + ks;
-  const int kbeg = min(K1, kidx * kchunk);
-  const int kend = min(K1, (kidx + 1) * kchunk);
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const bf16_t* brow = W1pk + (long)(wg * 4 + g) * JB * K1;
-  NATS_MFMA_KLOOP(acc, hc_bf, 16 * m, K1, brow, 0, K1, kbeg, kend);
-  store_cd_lds(pre[g][ks], acc, 16 * m);
+  const int j0 = blockIdx.x * JB;
+  gru1_mfma_phase(pre, hc_bf, W1pk, K1, blockIdx.x, ksb, gridDim.y);
   __syncthreads();
 
   float* dst = part + ((long)ksb * 4 + 0) * 32 * Hpad;
@@ -480,15 +484,8 @@ __global__ void cond_gru1_step_pointwise(
       p2 += pk[(long)2 * 32 * Hpad + bj];
       p3 += pk[(long)3 * 32 * Hpad + bj];
     }
-    const float pxa = p2;
-    const GruCellFwd o = gru_cell_fwd(p0 + b1[j], p1 + b1[H + j],
-                                      pxa + bx1[j], p3, h1_t[idx], mask_t, b);
-    h2_t[idx] = o.hnew;
-    h2bf_out[(long)b * ld_h2bf + j] = (bf16_t)o.hnew;
-    saved1_t[(long)b * 4 * H + j] = o.r;
-    saved1_t[(long)b * 4 * H + H + j] = o.u;
-    saved1_t[(long)b * 4 * H + 2 * H + j] = pxa;
-    saved1_t[(long)b * 4 * H + 3 * H + j] = o.hbar;
+    gru1_fwd_finish(p0, p1, p2, p3, h1_t, b1, bx1, mask_t, h2_t, h2bf_out,
+                    ld_h2bf, saved1_t, H, b, j);
   }
 }
 
@@ -581,7 +578,6 @@ __global__ __launch_bounds__(384) void cond_bwd_gemm_dual_gate(
   // fold in here (block-local b-reduction + one atomic per column per
   // step) — the torch expression re-streamed three (T,B,C) buffers
   __shared__ float ucon_s[JB], wcon_s[JB];
-  __shared__ float part[3][32][JB + 1];
   const bool ctx_side = (blockIdx.y == 1);
   if (ctx_side && threadIdx.x < JB) {
     ucon_s[threadIdx.x] = 0.f;
@@ -592,26 +588,10 @@ __global__ __launch_bounds__(384) void cond_bwd_gemm_dual_gate(
   const bf16_t* dstep = ctx_side ? dstepC : dstep1;
   const bf16_t* Wt = ctx_side ? W1cat : U1cat;
 
-  const int wg = blockIdx.x;
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 3;
-  const int ks = wave % 3;
-  const int i0 = wg * JB;
-  const int kchunk = ((Kpad / 3 + 31) / 32) * 32;
-  const int kbeg = ks * kchunk;
-  const int kend = min(Kpad, (ks + 1) * kchunk);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  NATS_MFMA_KLOOP(acc, dstep, 16 * m, Kpad, Wt, i0, Kpad, kbeg, kend);
-  store_cd_lds(part[ks], acc, 16 * m);
-  __syncthreads();
-
-  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
-    const int b = idx / JB;
-    const int cc = idx % JB;
-    const int i = i0 + cc;
-    if (i >= N) continue;
+  const int i0 = blockIdx.x * JB;
+  row_gemm(dstep, Wt, i0, Kpad, KRange{0, Kpad}, B, N,
+           [&](int b, int i, float sum) {
     const long bi = (long)b * N + i;
-    const float sum = part[0][b][cc] + part[1][b][cc] + part[2][b][cc];
     if (!ctx_side) {
       dh1_buf[bi] = ddirect_h1[bi] + sum;
     } else {
@@ -622,10 +602,10 @@ __global__ __launch_bounds__(384) void cond_bwd_gemm_dual_gate(
       dctxpre_f32[bi] = dpre;
       dctxpre_all_t[bi] = (bf16_t)dpre;
       daccC[bi] += dg * Wcon[i];
-      atomicAdd(ucon_s + cc, dg * (float)ctxpre_t[bi]);
-      atomicAdd(wcon_s + cc, dg * (float)accC_used_t[bi]);
+      atomicAdd(ucon_s + (i - i0), dg * (float)ctxpre_t[bi]);
+      atomicAdd(wcon_s + (i - i0), dg * (float)accC_used_t[bi]);
     }
-  }
+  });
   if (ctx_side) {
     __syncthreads();
     if (threadIdx.x < JB && i0 + (int)threadIdx.x < N) {
@@ -665,35 +645,19 @@ __global__ __launch_bounds__(384) void cond_dh_carry_gemm_split(
     const float* __restrict__ ddirect, // [B][H] (added by grid.y == 0)
     float* __restrict__ out,           // [2][B][H] partials
     int B, int H, int Kpad) {
-  __shared__ float part[3][32][JB + 1];
-  const int wg = blockIdx.x;
   const int ks2 = blockIdx.y;        // K half
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 3;
-  const int ks = wave % 3;
-  const int i0 = wg * JB;
-  const int khalf = ((Kpad / 2 + 31) / 32) * 32;
-  const int hbeg = min(Kpad, ks2 * khalf);
-  const int hend = min(Kpad, hbeg + khalf);
-  const int kchunk = (((hend - hbeg) / 3 + 31) / 32) * 32;
-  const int kbeg = hbeg + ks * kchunk;
-  const int kend = min(hend, kbeg + kchunk);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  NATS_MFMA_KLOOP(acc, dstep, 16 * m, Kpad, Wt, i0, Kpad, kbeg, kend);
-  store_cd_lds(part[ks], acc, 16 * m);
-  __syncthreads();
   float* o = out + (long)ks2 * B * H;
-  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
-    const int b = idx / JB;
-    const int cc = idx % JB;
-    const int i = i0 + cc;
-    if (i >= H) continue;
-    float v = part[0][b][cc] + part[1][b][cc] + part[2][b][cc];
-    if (ks2 == 0) v += ddirect[(long)b * H + i];
-    o[(long)b * H + i] = v;
-  }
+  row_gemm(dstep, Wt, blockIdx.x * JB, Kpad,
+           k_part(KRange{0, Kpad}, 2, ks2), B, H,
+           [&](int b, int i, float v) {
+             if (ks2 == 0) v += ddirect[(long)b * H + i];
+             o[(long)b * H + i] = v;
+           });
 }
 
+// Same wave map and epilogue shape as row_gemm, kept written out: its A
+// fragments are converted from fp32 in-register (frag_a_f32pad) under a
+// plain K-loop, which row_gemm's pipelined bf16 loop cannot express.
 __global__ __launch_bounds__(384) void cond_dh1_att_gemm(
     const float* __restrict__ dpstate_t,  // [B][A] fp32 (atomic-reduced)
     const bf16_t* __restrict__ WattB,     // [ngrpH*16][Apad]
@@ -705,11 +669,9 @@ __global__ __launch_bounds__(384) void cond_dh1_att_gemm(
   const int m = wave / 3;
   const int ks = wave % 3;
   const int i0 = wg * JB;
-  const int kchunk = ((Apad / 3 + 31) / 32) * 32;
-  const int kbeg = ks * kchunk;
-  const int kend = min(Apad, (ks + 1) * kchunk);
+  const KRange kr = k_part(KRange{0, Apad}, 3, ks);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k = kbeg; k + 32 <= kend; k += 32) {
+  for (int k = kr.beg; k + 32 <= kr.end; k += 32) {
     bf16x8 a = frag_a_f32pad(dpstate_t, 16 * m, A, k, B, A);
     bf16x8 bfr = frag_bt_rowmajor(WattB, i0, Apad, k);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, acc, 0, 0, 0);
@@ -920,14 +882,14 @@ std::vector<torch::Tensor> cond_gru_fwd(
   const int Ts = ctx_bf.size(0), C = ctx_bf.size(2);
   const int A = Uatt.size(0);
   TORCH_CHECK(B <= 32, "cond_gru: batch must be <= 32");
-  TORCH_CHECK(yg.dtype() == torch::kBFloat16 && yg.is_contiguous());
-  TORCH_CHECK(ctx_bf.dtype() == torch::kBFloat16 && ctx_bf.is_contiguous());
-  TORCH_CHECK(pctx.dtype() == torch::kFloat32 && pctx.is_contiguous());
+  check_scan_input(yg, torch::kBFloat16, "cond_gru yg");
+  check_scan_input(ctx_bf, torch::kBFloat16, "cond_gru ctx");
+  check_scan_input(pctx, torch::kFloat32, "cond_gru pctx");
   const int Hpad = Upk2.size(1);
   const int K1 = W1pk.size(1);
   const int ngrpH = cdiv(H, JB);
-  TORCH_CHECK(Upk2.size(0) == ngrpH * 3 * JB);
-  TORCH_CHECK(W1pk.size(0) == ngrpH * 4 * JB);
+  check_packed_weight(Upk2, H, 3, "cond_gru Upk2");
+  check_packed_weight(W1pk, H, 4, "cond_gru W1pk");
 
   auto optsF = yg.options().dtype(torch::kFloat32);
   auto optsB = yg.options();
@@ -967,48 +929,41 @@ std::vector<torch::Tensor> cond_gru_fwd(
   h2bf[0].slice(0, 0, B).slice(1, 0, H).copy_(init_f.to(torch::kBFloat16));
 
   const OptF32 mask_f(mask), cmask_f(ctx_mask);
-  const float* mask_p = mask_f.p;
   const float* cmask_p = cmask_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   const int Apad16 = cdiv(A, 16) * 16;
-  const long hbstride = (long)32 * Hpad;
-  bf16_t* h2bf_p = (bf16_t*)h2bf.data_ptr();
+  const Steps<const bf16_t> yg_s(yg), yc_s(yc);
+  const Steps<const float> mask_s(mask_f.t);
+  const Steps<float> h1_s(h1_all), h2_s(h2_all), saved1_s(saved1),
+      ctxs_s(ctxs_all), alphas_s(alphas_all), accA_used_s(accA_used),
+      pstate_s(pstate_all);
+  const Steps<bf16_t> saved2_s(saved2), accC_used_s(accC_used),
+      ctxpre_s(ctxpre_all), h2bf_s(h2bf);  // h2bf: the ping-pong pair
+  bf16_t* hc_bf_p = (bf16_t*)hc_bf.data_ptr();
+  const bf16_t* Upk2_p = (const bf16_t*)Upk2.data_ptr();
 
   for (int t = 0; t < T; ++t) {
-    const float* h2prev = (t == 0)
-                              ? init_f.data_ptr<float>()
-                              : h2_all.data_ptr<float>() + (long)(t - 1) * B * H;
-    const float* mt = mask_p ? mask_p + (long)t * B : nullptr;
+    const float* h2prev = t == 0 ? init_f.data_ptr<float>() : h2_s.at(t - 1);
+    const float* mt = mask_s.at(t);
     // 1) GRU_2 -> h1 (bf16 into hc_bf cols [0,H)); split-K when K large
     if (Hpad >= 1024) {
       hipLaunchKernelGGL(nats_gru2_gemm_splitk, dim3(ngrpH, GRU2_KS),
-                         dim3(384), 0, stream, h2bf_p + (t % 2) * hbstride,
-                         (const bf16_t*)Upk2.data_ptr(),
+                         dim3(384), 0, stream, h2bf_s.at(t % 2), Upk2_p,
                          gru2_part.data_ptr<float>(), Hpad);
       hipLaunchKernelGGL(nats_gru2_step_pointwise, dim3(cdiv(B * H, 256)),
                          dim3(256), 0, stream, gru2_part.data_ptr<float>(),
-                         GRU2_KS, h2prev,
-                         (const bf16_t*)yg.data_ptr() + (long)t * B * 2 * H,
-                         (const bf16_t*)yc.data_ptr() + (long)t * B * H, mt,
-                         h1_all.data_ptr<float>() + (long)t * B * H,
-                         (bf16_t*)hc_bf.data_ptr(), K1,
-                         (bf16_t*)saved2.data_ptr() + (long)t * B * 3 * H, B,
-                         H, Hpad);
+                         GRU2_KS, h2prev, yg_s.at(t), yc_s.at(t), mt,
+                         h1_s.at(t), hc_bf_p, K1, saved2_s.at(t), B, H, Hpad);
     } else {
       hipLaunchKernelGGL(nats_gru_step_fwd, dim3(ngrpH), dim3(384), 0, stream,
-                         h2bf_p + (t % 2) * hbstride, h2prev,
-                         (const bf16_t*)Upk2.data_ptr(),
-                         (const bf16_t*)yg.data_ptr() + (long)t * B * 2 * H,
-                         (const bf16_t*)yc.data_ptr() + (long)t * B * H, mt,
-                         h1_all.data_ptr<float>() + (long)t * B * H,
-                         (bf16_t*)hc_bf.data_ptr(), K1,
-                         (bf16_t*)saved2.data_ptr() + (long)t * B * 3 * H, B,
-                         H, Hpad);
+                         h2bf_s.at(t % 2), h2prev, Upk2_p, yg_s.at(t),
+                         yc_s.at(t), mt, h1_s.at(t), hc_bf_p, K1,
+                         saved2_s.at(t), B, H, Hpad);
     }
     // 2) pstate = h1 @ W_att (split-K partials; summed by the consumers)
     hipLaunchKernelGGL(cond_small_gemm_bt, dim3(2, Apad16 / 16, PS_KS),
-                       dim3(64), 0, stream, (const bf16_t*)hc_bf.data_ptr(),
+                       dim3(64), 0, stream, hc_bf_p,
                        (const bf16_t*)WattPk.data_ptr(),
                        ps_part.data_ptr<float>(), B, A, K1,
                        (int)WattPk.size(1));
@@ -1020,52 +975,40 @@ std::vector<torch::Tensor> cond_gru_fwd(
                        accA.data_ptr<float>(), Dwei.data_ptr<float>(),
                        Uatt.data_ptr<float>(), catt.data_ptr<float>(),
                        cmask_p, (const bf16_t*)ctx_bf.data_ptr(),
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       att_stats.data_ptr<float>(),
+                       alphas_s.at(t), att_stats.data_ptr<float>(),
                        ctx_part.data_ptr<float>(), B, Ts, A, C, CH, lps);
     // 4) attention pass 2: global softmax statistics, combined context,
     // gate + acc_ctx, normalised alphas + acc_alpha, combined pstate
     hipLaunchKernelGGL(cond_attn_combine_gate, dim3(B, cdiv(C, ATT_THREADS)),
                        dim3(ATT_THREADS), NCH * sizeof(float), stream,
                        att_stats.data_ptr<float>(),
-                       ctx_part.data_ptr<float>(), NCH, CH,
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       accA.data_ptr<float>(),
-                       accA_used.data_ptr<float>() + (long)t * B * Ts,
-                       ps_part.data_ptr<float>(), PS_KS,
-                       pstate_all.data_ptr<float>() + (long)t * B * A, A, Ts,
-                       Ucon.data_ptr<float>(), Wcon.data_ptr<float>(),
-                       accC.data_ptr<float>(),
-                       (bf16_t*)accC_used.data_ptr() + (long)t * B * C,
-                       (bf16_t*)ctxpre_all.data_ptr() + (long)t * B * C,
-                       ctxs_all.data_ptr<float>() + (long)t * B * C,
-                       (bf16_t*)hc_bf.data_ptr(), Hpad, K1, mt, B, C);
+                       ctx_part.data_ptr<float>(), NCH, CH, alphas_s.at(t),
+                       accA.data_ptr<float>(), accA_used_s.at(t),
+                       ps_part.data_ptr<float>(), PS_KS, pstate_s.at(t), A,
+                       Ts, Ucon.data_ptr<float>(), Wcon.data_ptr<float>(),
+                       accC.data_ptr<float>(), accC_used_s.at(t),
+                       ctxpre_s.at(t), ctxs_s.at(t), hc_bf_p, Hpad, K1, mt, B,
+                       C);
     // 5) GRU_1 -> h2: split-K for large K (raises block parallelism 4x),
     // single fused kernel when K is small (split overhead dominates)
     if (K1 >= 2048) {
       hipLaunchKernelGGL(cond_gru1_gemm_splitk, dim3(ngrpH, GRU1_KS),
-                         dim3(1024), 0, stream,
-                         (const bf16_t*)hc_bf.data_ptr(),
+                         dim3(1024), 0, stream, hc_bf_p,
                          (const bf16_t*)W1pk.data_ptr(),
                          gru1_part.data_ptr<float>(), H, K1, Hpad);
       hipLaunchKernelGGL(cond_gru1_step_pointwise, dim3(cdiv(B * H, 256)),
                          dim3(256), 0, stream, gru1_part.data_ptr<float>(),
-                         GRU1_KS, h1_all.data_ptr<float>() + (long)t * B * H,
-                         b1.data_ptr<float>(), bx1.data_ptr<float>(), mt,
-                         h2_all.data_ptr<float>() + (long)t * B * H,
-                         h2bf_p + ((t + 1) % 2) * hbstride, Hpad,
-                         saved1.data_ptr<float>() + (long)t * B * 4 * H, B,
-                         H, Hpad);
+                         GRU1_KS, h1_s.at(t), b1.data_ptr<float>(),
+                         bx1.data_ptr<float>(), mt, h2_s.at(t),
+                         h2bf_s.at((t + 1) % 2), Hpad, saved1_s.at(t), B, H,
+                         Hpad);
     } else {
       hipLaunchKernelGGL(cond_gru1_step_fwd, dim3(ngrpH), dim3(1024), 0,
-                         stream, (const bf16_t*)hc_bf.data_ptr(),
-                         h1_all.data_ptr<float>() + (long)t * B * H,
+                         stream, hc_bf_p, h1_s.at(t),
                          (const bf16_t*)W1pk.data_ptr(), b1.data_ptr<float>(),
-                         bx1.data_ptr<float>(), mt,
-                         h2_all.data_ptr<float>() + (long)t * B * H,
-                         h2bf_p + ((t + 1) % 2) * hbstride, Hpad,
-                         saved1.data_ptr<float>() + (long)t * B * 4 * H, B,
-                         H, K1);
+                         bx1.data_ptr<float>(), mt, h2_s.at(t),
+                         h2bf_s.at((t + 1) % 2), Hpad, saved1_s.at(t), B, H,
+                         K1);
     }
   }
   HIP_CHECK(hipGetLastError());
@@ -1099,6 +1042,16 @@ std::vector<torch::Tensor> cond_gru_bwd(
   const int Apad32 = WattB.size(1);
   const int ngrpH = cdiv(H, JB);
   const int ngrpC = cdiv(C, JB);
+  // what cond_gru_fwd checks, for the tensors this side reads
+  TORCH_CHECK(B <= 32, "cond_gru: batch must be <= 32");
+  check_scan_input(yc, torch::kBFloat16, "cond_gru yc");
+  check_scan_input(saved2, torch::kBFloat16, "cond_gru saved2");
+  check_scan_input(ctx_bf, torch::kBFloat16, "cond_gru ctx");
+  check_scan_input(pctx, torch::kFloat32, "cond_gru pctx");
+  check_packed_weight(U1cat, H, 1, "cond_gru U1cat");
+  check_packed_weight(W1cat, C, 1, "cond_gru W1cat");
+  check_packed_weight(U2cat, H, 1, "cond_gru U2cat");
+  check_packed_weight(WattB, H, 1, "cond_gru WattB");
 
   auto optsF = dh2_all.options().dtype(torch::kFloat32);
   auto optsB = dh2_all.options().dtype(torch::kBFloat16);
@@ -1140,35 +1093,34 @@ std::vector<torch::Tensor> cond_gru_bwd(
   auto init_f = init_state.contiguous().to(torch::kFloat32);
 
   const OptF32 mask_f(mask), dctxs_f(dctxs_all), dalpha_f(dalphas_all);
-  const float* mask_all = mask_f.p;
-  const float* dctxs_p = dctxs_f.p;
-  const float* dalpha_p = dalpha_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   auto dh2_c = dh2_all.contiguous().to(torch::kFloat32);
   const int pwH = (int)std::min<long>(512, (((long)B * H) + 255) / 256);
   const int pwHC =
       (int)std::min<long>(512, (((long)B * (H + C)) + 255) / 256);
+  const Steps<const float> mask_s(mask_f.t), dctxs_s(dctxs_f.t),
+      dalpha_s(dalpha_f.t), dh2_s(dh2_c), h1_s(h1_all), h2_s(h2_all),
+      saved1_s(saved1), ctxs_s(ctxs_all), alphas_s(alphas_all),
+      pstate_s(pstate_all), accA_used_s(accA_used);
+  const Steps<const bf16_t> yc_s(yc), saved2_s(saved2), ctxpre_s(ctxpre_all),
+      accC_used_s(accC_used);
+  const Steps<bf16_t> dpre1_s(dpre1_all), dpre2_s(dpre2_all),
+      dctxpre_s(dctxpre_all);
+  const Steps<float> dpstate_s(dpstate_all), dh_carry_s(dh_carry);  // K halves
 
   for (int t = T - 1; t >= 0; --t) {
-    const float* mt = mask_all ? mask_all + (long)t * B : nullptr;
-    const float* h2prev =
-        (t == 0) ? init_f.data_ptr<float>()
-                 : h2_all.data_ptr<float>() + (long)(t - 1) * B * H;
+    const float* mt = mask_s.at(t);
+    const float* h2prev = t == 0 ? init_f.data_ptr<float>() : h2_s.at(t - 1);
     // b1 (fused): GRU_1 pointwise + dctx passthrough
     hipLaunchKernelGGL(cond_gru1_bwd_pointwise, dim3(pwHC), dim3(256), 0,
-                       stream, dh_carry.data_ptr<float>(),
-                       dh_carry.data_ptr<float>() + (long)B * H,
-                       dh2_c.data_ptr<float>() + (long)t * B * H,
-                       saved1.data_ptr<float>() + (long)t * B * 4 * H,
-                       h1_all.data_ptr<float>() + (long)t * B * H,
+                       stream, dh_carry_s.at(0), dh_carry_s.at(1),
+                       dh2_s.at(t), saved1_s.at(t), h1_s.at(t),
                        bx1.data_ptr<float>(), mt,
                        (bf16_t*)dstep1.data_ptr(), (bf16_t*)dstepC.data_ptr(),
-                       K3Hpad, ddirect_h1.data_ptr<float>(),
-                       (bf16_t*)dpre1_all.data_ptr() + (long)t * B * 4 * H,
-                       dctxs_p ? dctxs_p + (long)t * B * C : nullptr,
-                       daccC.data_ptr<float>(), dctx_dir.data_ptr<float>(), C,
-                       B, H);
+                       K3Hpad, ddirect_h1.data_ptr<float>(), dpre1_s.at(t),
+                       dctxs_s.at(t), daccC.data_ptr<float>(),
+                       dctx_dir.data_ptr<float>(), C, B, H);
     // b2+b3+b4 fused launch: dh1 = ddirect_h1 + dstep1 @ [U_1|Ux_1]^T and
     // the dctx GEMM with the distraction-gate backward applied in the
     // epilogue (the former separate cond_gate_bwd pass)
@@ -1180,13 +1132,10 @@ std::vector<torch::Tensor> cond_gru_bwd(
                        dh1_buf.data_ptr<float>(), H,
                        (const bf16_t*)dstepC.data_ptr(),
                        (const bf16_t*)W1cat.data_ptr(),
-                       dctx_dir.data_ptr<float>(), C, K3Hpad,
-                       ctxs_all.data_ptr<float>() + (long)t * B * C,
+                       dctx_dir.data_ptr<float>(), C, K3Hpad, ctxs_s.at(t),
                        Ucon.data_ptr<float>(), Wcon.data_ptr<float>(),
                        daccC.data_ptr<float>(), dctxpre_f32.data_ptr<float>(),
-                       (bf16_t*)dctxpre_all.data_ptr() + (long)t * B * C,
-                       (const bf16_t*)ctxpre_all.data_ptr() + (long)t * B * C,
-                       (const bf16_t*)accC_used.data_ptr() + (long)t * B * C,
+                       dctxpre_s.at(t), ctxpre_s.at(t), accC_used_s.at(t),
                        gdUcon.data_ptr<float>(), gdWcon.data_ptr<float>(),
                        B);
     // b5: attention backward — wave-per-(b,s) dalpha, then one pass per
@@ -1195,36 +1144,28 @@ std::vector<torch::Tensor> cond_gru_bwd(
     hipLaunchKernelGGL(cond_attn_bwd_dalpha, dim3(B, cdiv(Ts, 4)),
                        dim3(256), 0, stream,
                        (const bf16_t*)ctx_bf.data_ptr(),
-                       dctxpre_f32.data_ptr<float>(),
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       daccA.data_ptr<float>(), mt,
-                       dalpha_p ? dalpha_p + (long)t * B * Ts : nullptr,
+                       dctxpre_f32.data_ptr<float>(), alphas_s.at(t),
+                       daccA.data_ptr<float>(), mt, dalpha_s.at(t),
                        dal_buf.data_ptr<float>(), B, Ts, C);
     hipLaunchKernelGGL(cond_attn_bwd_fused, dim3(B, NCH), dim3(ATT_THREADS),
                        (3 * A4 + 2 * CH * A) * sizeof(float), stream,
-                       alphas_all.data_ptr<float>() + (long)t * B * Ts,
-                       dal_buf.data_ptr<float>(), pctx.data_ptr<float>(),
-                       pstate_all.data_ptr<float>() + (long)t * B * A,
-                       accA_used.data_ptr<float>() + (long)t * B * Ts,
-                       Dwei.data_ptr<float>(), Uatt.data_ptr<float>(),
-                       daccA.data_ptr<float>(), dpctx_acc.data_ptr<float>(),
-                       dpstate_all.data_ptr<float>() + (long)t * B * A,
+                       alphas_s.at(t), dal_buf.data_ptr<float>(),
+                       pctx.data_ptr<float>(), pstate_s.at(t),
+                       accA_used_s.at(t), Dwei.data_ptr<float>(),
+                       Uatt.data_ptr<float>(), daccA.data_ptr<float>(),
+                       dpctx_acc.data_ptr<float>(), dpstate_s.at(t),
                        gslot.data_ptr<float>(), B, Ts, A, CH, lps);
     // b6a: dh1 += dpstate @ W_att^T — A fragments converted from the
     // fp32 dpstate in-register (no cond_dpstate_cast pass)
     hipLaunchKernelGGL(cond_dh1_att_gemm, dim3(ngrpH), dim3(384), 0, stream,
-                       dpstate_all.data_ptr<float>() + (long)t * B * A,
-                       (const bf16_t*)WattB.data_ptr(),
+                       dpstate_s.at(t), (const bf16_t*)WattB.data_ptr(),
                        dh1_buf.data_ptr<float>(), B, H, A, Apad32);
     // b8: GRU_2 pointwise (dh1 -> gate preact grads)
     hipLaunchKernelGGL(nats_gru_step_bwd_pointwise, dim3(pwH), dim3(256), 0,
                        stream, dh1_buf.data_ptr<float>(), nullptr,
-                       (const bf16_t*)saved2.data_ptr() + (long)t * B * 3 * H,
-                       (const bf16_t*)yc.data_ptr() + (long)t * B * H, h2prev,
-                       mt, (bf16_t*)dstep2.data_ptr(), K3Hpad,
-                       ddirect2.data_ptr<float>(),
-                       (bf16_t*)dpre2_all.data_ptr() + (long)t * B * 4 * H, B,
-                       H);
+                       saved2_s.at(t), yc_s.at(t), h2prev, mt,
+                       (bf16_t*)dstep2.data_ptr(), K3Hpad,
+                       ddirect2.data_ptr<float>(), dpre2_s.at(t), B, H);
     // b9: dh_{t-1} = [dpr1|dpu1|dpxl1] @ [U|Ux]^T + passthrough, split
     // over K halves written as two partials (summed by the next step's
     // GRU_1 pointwise — no atomics, no zeroing)

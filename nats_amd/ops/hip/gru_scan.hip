@@ -32,6 +32,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include "common.h"
+#include "grid_barrier.h"
 #include "gru_kernels.h"
 
 // ---------------- forward step ----------------
@@ -57,17 +58,8 @@ __device__ __forceinline__ void gru_fwd_body(const GruFwdArgs& a,
     const int c = idx % JB;
     const int j = j0 + c;
     if (j >= H) continue;
-    const float hp = a.h_prev[(long)b * H + j];
-    const float pr = pre[0][b][c] + (float)a.xg_t[(long)b * 2 * H + j];
-    const float pu = pre[1][b][c] + (float)a.xg_t[(long)b * 2 * H + H + j];
-    const float px = pre[2][b][c];
-    const GruCellFwd o = gru_cell_fwd(
-        pr, pu, px, (float)a.xc_t[(long)b * H + j], hp, a.mask_t, b);
-    a.h_out[(long)b * H + j] = o.hnew;
-    a.h_bf_out[(long)b * ld_bfout + j] = (bf16_t)o.hnew;
-    a.saved_t[(long)b * 3 * H + j] = (bf16_t)o.r;
-    a.saved_t[(long)b * 3 * H + H + j] = (bf16_t)o.u;
-    a.saved_t[(long)b * 3 * H + 2 * H + j] = (bf16_t)px;
+    gru_fwd_finish(a, ld_bfout, H, b, j, (long)b * H + j, pre[0][b][c],
+                   pre[1][b][c], pre[2][b][c]);
   }
 }
 
@@ -111,12 +103,10 @@ __global__ __launch_bounds__(384) void nats_gru2_gemm_splitk(
   const int wave = threadIdx.x / NATS_WAVE;
   const int m = wave / 3;
   const int g = wave % 3;
-  const int kchunk = ((Hpad / KS + 31) / 32) * 32;
-  const int kbeg = min(Hpad, ksb * kchunk);
-  const int kend = min(Hpad, kbeg + kchunk);
+  const KRange k = k_part(KRange{0, Hpad}, KS, ksb);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const bf16_t* brow = Upk + (long)(wg * 3 + g) * JB * Hpad;
-  NATS_MFMA_KLOOP(acc, h_bf, 16 * m, Hpad, brow, 0, Hpad, kbeg, kend);
+  NATS_MFMA_KLOOP(acc, h_bf, 16 * m, Hpad, brow, 0, Hpad, k.beg, k.end);
   store_cd_rowmajor(part + ((long)ksb * 3 + g) * 32 * Hpad, acc, 16 * m,
                     Hpad, wg * JB);
 }
@@ -146,17 +136,9 @@ __global__ void nats_gru2_step_pointwise(
       p1 += pk[(long)32 * Hpad + bj];
       p2 += pk[(long)2 * 32 * Hpad + bj];
     }
-    const float hp = h_prev[idx];
-    const float pr = p0 + (float)xg_t[(long)b * 2 * H + j];
-    const float pu = p1 + (float)xg_t[(long)b * 2 * H + H + j];
-    const float px = p2;
-    const GruCellFwd o =
-        gru_cell_fwd(pr, pu, px, (float)xc_t[idx], hp, mask_t, b);
-    h_out[idx] = o.hnew;
-    h_bf_out[(long)b * ld_bfout + j] = (bf16_t)o.hnew;
-    saved_t[(long)b * 3 * H + j] = (bf16_t)o.r;
-    saved_t[(long)b * 3 * H + H + j] = (bf16_t)o.u;
-    saved_t[(long)b * 3 * H + 2 * H + j] = (bf16_t)px;
+    gru_fwd_finish(GruFwdArgs{nullptr, h_prev, nullptr, xg_t, xc_t, mask_t,
+                              h_out, h_bf_out, saved_t},
+                   ld_bfout, H, b, j, idx, p0, p1, p2);
   }
 }
 
@@ -178,23 +160,9 @@ __global__ void nats_gru_step_bwd_pointwise(
        idx += (long)gridDim.x * blockDim.x) {
     const int b = idx / H;
     const int j = idx % H;
-    float dh = dh_buf[idx];
-    if (dh_out_t != nullptr) dh += dh_out_t[idx];
-    const float r = (float)saved_t[(long)b * 3 * H + j];
-    const float u = (float)saved_t[(long)b * 3 * H + H + j];
-    const float px = (float)saved_t[(long)b * 3 * H + 2 * H + j];
-    const float hbar = tanhf(px * r + (float)xc_t[idx]);
-    const float hp = h_prev[idx];
-    const float mm = (mask_t != nullptr) ? mask_t[b] : 1.f;
-    const GruCellBwd o = gru_cell_bwd(dh, r, u, px, hbar, hp, mm);
-    ddirect[idx] = o.ddirect;
-    dstep[(long)b * ld_dstep + j] = (bf16_t)o.dpr;
-    dstep[(long)b * ld_dstep + H + j] = (bf16_t)o.dpu;
-    dstep[(long)b * ld_dstep + 2 * H + j] = (bf16_t)o.dpxl;
-    dpre_t[(long)b * 4 * H + j] = (bf16_t)o.dpr;
-    dpre_t[(long)b * 4 * H + H + j] = (bf16_t)o.dpu;
-    dpre_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)o.dpx;
-    dpre_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.dpxl;
+    gru_bwd_finish(GruBwdArgs{nullptr, nullptr, dh_out_t, saved_t, xc_t,
+                              h_prev, mask_t, dstep, ddirect, dpre_t},
+                   ld_dstep, H, b, j, idx, dh_buf[idx]);
   }
 }
 
@@ -202,47 +170,12 @@ __global__ void nats_gru_step_bwd_pointwise(
 __device__ __forceinline__ void gru_bwd_fused_body(const GruBwdArgs& a,
                                                    const bf16_t* Ubwd, int B,
                                                    int H, int Kpad, int wg) {
-  __shared__ float part[3][32][JB + 1];
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 3;
-  const int ks = wave % 3;
-  const int i0 = wg * JB;
-
-  const int kchunk = ((Kpad / 3 + 31) / 32) * 32;
-  const int kbeg = ks * kchunk;
-  const int kend = min(Kpad, (ks + 1) * kchunk);
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  NATS_MFMA_KLOOP(acc, a.dstep_in, 16 * m, Kpad, Ubwd, i0, Kpad, kbeg, kend);
-  store_cd_lds(part[ks], acc, 16 * m);
-  __syncthreads();
-
-  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
-    const int b = idx / JB;
-    const int c = idx % JB;
-    const int j = i0 + c;
-    if (j >= H) continue;
-    const long bj = (long)b * H + j;
-    // dh at step t for column j (recurrent + passthrough + upstream)
-    float dh = a.ddirect_in[bj] + part[0][b][c] + part[1][b][c] +
-               part[2][b][c];
-    if (a.dh_out_t != nullptr) dh += a.dh_out_t[bj];
-    const float r = (float)a.saved_t[(long)b * 3 * H + j];
-    const float u = (float)a.saved_t[(long)b * 3 * H + H + j];
-    const float px = (float)a.saved_t[(long)b * 3 * H + 2 * H + j];
-    const float hbar = tanhf(px * r + (float)a.xc_t[bj]);
-    const float hp = a.h_prev[bj];
-    const float mm = (a.mask_t != nullptr) ? a.mask_t[b] : 1.f;
-    const GruCellBwd o = gru_cell_bwd(dh, r, u, px, hbar, hp, mm);
-    a.ddirect_out[bj] = o.ddirect;
-    a.dstep_out[(long)b * Kpad + j] = (bf16_t)o.dpr;
-    a.dstep_out[(long)b * Kpad + H + j] = (bf16_t)o.dpu;
-    a.dstep_out[(long)b * Kpad + 2 * H + j] = (bf16_t)o.dpxl;
-    a.dpre_t[(long)b * 4 * H + j] = (bf16_t)o.dpr;
-    a.dpre_t[(long)b * 4 * H + H + j] = (bf16_t)o.dpu;
-    a.dpre_t[(long)b * 4 * H + 2 * H + j] = (bf16_t)o.dpx;
-    a.dpre_t[(long)b * 4 * H + 3 * H + j] = (bf16_t)o.dpxl;
-  }
+  row_gemm(a.dstep_in, Ubwd, wg * JB, Kpad, KRange{0, Kpad}, B, H,
+           [&](int b, int j, float sum) {
+             // dh at step t for column j: recurrent + passthrough
+             const long bj = (long)b * H + j;
+             gru_bwd_finish(a, Kpad, H, b, j, bj, a.ddirect_in[bj] + sum);
+           });
 }
 
 __global__ __launch_bounds__(384) void nats_gru_step_bwd_fused_bidir(
@@ -263,142 +196,6 @@ __global__ __launch_bounds__(384) void nats_gru_step_bwd_fused_bidir(
 // an agent-scope release/acquire grid barrier per step (guide §6 G16:
 // placement-independent, bounded spin with a give-up flag the host
 // checks — a barrier bug aborts instead of hanging the box).
-
-// XCD-hierarchical grid barrier (microarch 'barrier-xcd' scheme). Blocks
-// are bucketed by their REAL XCC id (s_getreg XCC_ID, gfx942/950 —
-// amd_device_functions.h:754-793), established once by a census at kernel
-// start (nats_barrier_init). Per barrier, only the LAST ARRIVER of each
-// XCD executes the agent-release fence (ONE buffer_wbl2 L2 writeback per
-// XCD instead of one per block — the per-block variant measured 7.8us at
-// 126 WGs / 12.1us at 256; see profiles/barrier_bench.json); it then
-// arrives at the top counter, acquire-fences, and publishes the XCD's
-// generation word. Non-leaders poll their XCD's generation word and
-// acquire-fence (buffer_inv) before returning. Correctness relies only on
-// bucket == physical XCD (true by construction from XCC_ID): the leader's
-// wbl2 flushes exactly the L2 holding its co-located blocks' drained
-// (vmcnt(0)) stores.
-//
-// Sync layout (zeroed per launch, NATS_SYNC_WORDS ints):
-//   [0..7]  per-XCD arrive counters (monotonic: nper*epoch)
-//   [8]     top counter (monotonic: nxcd*epoch)
-//   [9..16] per-XCD generation words
-//   [17]    give-up flag (checked by the host via NaN poisoning)
-//   [18..25] census: resident blocks per XCD
-//   [26]    census arrive counter
-
-struct NatsBarrierCtx {  // valid on thread 0 only
-  unsigned bucket;  // this block's physical XCD (0..7)
-  unsigned nper;    // blocks resident on this XCD
-  unsigned ntop;    // number of XCDs with >=1 block
-};
-
-__device__ __forceinline__ unsigned nats_xcc_id() {
-  // s_getreg_b32 XCC_ID[3:0] (hwreg 20), gfx942/950
-  return __builtin_amdgcn_s_getreg((3u << 11) | (0u << 6) | 20u) & 7u;
-}
-
-__device__ __forceinline__ bool nats_barrier_init(unsigned* sync,
-                                                  unsigned nwg,
-                                                  NatsBarrierCtx& ctx) {
-  __shared__ unsigned sh[4];
-  if (threadIdx.x == 0) {
-    const unsigned xcc = nats_xcc_id();
-    __hip_atomic_fetch_add(sync + 18 + xcc, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(sync + 26, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    unsigned ok = 1u, spins = 0u;
-    while (__hip_atomic_load(sync + 26, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT) < nwg) {
-      if (__hip_atomic_load(sync + 17, __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-          ++spins > 200000000u) {
-        __hip_atomic_store(sync + 17, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        ok = 0u;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    unsigned ntop = 0u;
-    for (int i = 0; i < 8; ++i)
-      ntop += (__hip_atomic_load(sync + 18 + i, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT) != 0u);
-    sh[0] = xcc;
-    sh[1] = __hip_atomic_load(sync + 18 + xcc, __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
-    sh[2] = ntop;
-    sh[3] = ok;
-  }
-  __syncthreads();
-  ctx.bucket = sh[0];
-  ctx.nper = sh[1];
-  ctx.ntop = sh[2];
-  return sh[3] != 0u;
-}
-
-__device__ __forceinline__ bool nats_grid_barrier(unsigned* sync,
-                                                  unsigned epoch,
-                                                  const NatsBarrierCtx& ctx) {
-  __shared__ unsigned ok_sh;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stores drained to L2
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned* arrive = sync + ctx.bucket;
-    unsigned* top = sync + 8;
-    unsigned* gen = sync + 9 + ctx.bucket;
-    unsigned* give_up = sync + 17;
-    unsigned ok = 1u, spins = 0u;
-
-    const unsigned prev = __hip_atomic_fetch_add(
-        arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev + 1u == ctx.nper * epoch) {
-      // last arriver on this XCD: one L2 writeback covers every
-      // co-located block's (already vmcnt-drained) stores
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-      for (;;) {
-        if (__hip_atomic_load(top, __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT) >= ctx.ntop * epoch)
-          break;
-        if (__hip_atomic_load(give_up, __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-            ++spins > 200000000u) {
-          __hip_atomic_store(give_up, 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-          ok = 0u;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      __hip_atomic_store(gen, epoch, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      for (;;) {
-        if (__hip_atomic_load(gen, __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT) >= epoch)
-          break;
-        if (__hip_atomic_load(give_up, __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-            ++spins > 200000000u) {
-          __hip_atomic_store(give_up, 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-          ok = 0u;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    ok_sh = ok;
-  }
-  __syncthreads();
-  return ok_sh != 0u;
-}
-
-#define NATS_SYNC_WORDS 27
 
 // stage a [rows][Kpad] bf16 slice into LDS with the (row&15)<<4 byte-XOR
 // swizzle; read back with the same XOR (write+read swizzled together).
@@ -526,10 +323,25 @@ __device__ __forceinline__ int nats_claim_job_slot(unsigned* claim,
   return sh_sel;
 }
 
+// Entry of both persistent kernels once a block holds claim `sel` (= job
+// << 16 | tile): move `sync` to the job's own barrier slab (jobs are
+// data-independent: each syncs only its own ngrp blocks), stage the tile's
+// weight rows in LDS, run the barrier census. False if the census gave up.
+// (The job pick stays a reference ternary in each kernel: through a helper
+// the four by-value job structs are copied into registers and spill.)
+__device__ __forceinline__ bool persist_enter(unsigned*& sync, int sel,
+                                              int ngrp, bf16_t* w_lds,
+                                              const bf16_t* w_tile, int rows,
+                                              int K, NatsBarrierCtx& bctx) {
+  sync += (long)(sel >> 16) * NATS_SYNC_WORDS;
+  stage_weights_lds(w_lds, w_tile, rows, K);
+  __syncthreads();
+  return nats_barrier_init(sync, (unsigned)ngrp, bctx);
+}
+
 __global__ __launch_bounds__(384) void nats_gru_persistent_fwd(
     GruPersistFwd p0, GruPersistFwd p1, GruPersistFwd p2, GruPersistFwd p3,
-    int T, int H, int Hpad, unsigned* sync, int ngrp, int njobs, int xpd,
-    int unsafe_nobarrier) {
+    int T, int H, int Hpad, unsigned* sync, int ngrp, int njobs, int xpd) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* upk_lds = (bf16_t*)smem;                       // [3*16][Hpad] swz
   float(*pre)[32][JB + 1] =
@@ -539,19 +351,14 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_fwd(
                                       ngrp, njobs, xpd);
   if (sel < 0) return;
   const int jobsel = sel >> 16;
-  const int wg = sel & 0xffff;
   const GruPersistFwd& p = (jobsel == 0) ? p0
                            : (jobsel == 1) ? p1
                            : (jobsel == 2) ? p2 : p3;
+  const int wg = sel & 0xffff;
   const int B = p.B;
-  // per-job barrier: jobs (direction x batch-chunk) are data-independent
-  // so each syncs only its own ngrp blocks (own sync slab)
-  sync += (long)jobsel * NATS_SYNC_WORDS;
-  unsigned nwg = (unsigned)ngrp;
-  stage_weights_lds(upk_lds, p.Upk + (long)wg * 3 * JB * Hpad, 3 * JB, Hpad);
-  __syncthreads();
   NatsBarrierCtx bctx;
-  if (!nats_barrier_init(sync, nwg, bctx)) {
+  if (!persist_enter(sync, sel, ngrp, upk_lds,
+                     p.Upk + (long)wg * 3 * JB * Hpad, 3 * JB, Hpad, bctx)) {
     if (threadIdx.x == 0) p.h_all[0] = __builtin_nanf("");
     return;
   }
@@ -640,9 +447,7 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_fwd(
     }
     pend_saved = p.saved + (long)t * p.ssaved;
     have_pend = true;
-    if (unsafe_nobarrier) {  // TIMING EXPERIMENTS ONLY (racy!)
-      __syncthreads();
-    } else if (!nats_grid_barrier(sync, (unsigned)(t + 1), bctx)) {
+    if (!nats_grid_barrier(sync, (unsigned)(t + 1), bctx)) {
       // poison output so a barrier give-up surfaces as NaN, never a hang
       if (threadIdx.x == 0) p.h_all[0] = __builtin_nanf("");
       return;
@@ -689,17 +494,14 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_bwd(
                                       ngrp, njobs, xpd);
   if (sel < 0) return;
   const int jobsel = sel >> 16;
-  const int wg = sel & 0xffff;
   const GruPersistBwd& p = (jobsel == 0) ? p0
                            : (jobsel == 1) ? p1
                            : (jobsel == 2) ? p2 : p3;
+  const int wg = sel & 0xffff;
   const int B = p.B;
-  sync += (long)jobsel * NATS_SYNC_WORDS;
-  unsigned nwg = (unsigned)ngrp;
-  stage_weights_lds(ub_lds, p.Ubwd + (long)wg * JB * K3pad, JB, K3pad);
-  __syncthreads();
   NatsBarrierCtx bctx;
-  if (!nats_barrier_init(sync, nwg, bctx)) {
+  if (!persist_enter(sync, sel, ngrp, ub_lds, p.Ubwd + (long)wg * JB * K3pad,
+                     JB, K3pad, bctx)) {
     if (threadIdx.x == 0) p.ddirect[0] = __builtin_nanf("");
     return;
   }
@@ -708,6 +510,8 @@ __global__ __launch_bounds__(384) void nats_gru_persistent_bwd(
   const int m = wave / 3;
   const int ks = wave % 3;
   const int i0 = wg * JB;
+  // k_part(KRange{0, K3pad}, 3, ks) with an unclamped kbeg: the clamp's
+  // extra v_min moves this kernel's register allocation
   const int kchunk = ((K3pad / 3 + 31) / 32) * 32;
   const int kbeg = ks * kchunk;
   const int kend = min(K3pad, (ks + 1) * kchunk);
@@ -831,57 +635,50 @@ __global__ __launch_bounds__(384) void nats_gru_step_bwd_gemm(
     const float* __restrict__ ddirect, // [B][H]
     float* __restrict__ out,           // [B][H] (may alias ddirect)
     int B, int H, int Kpad) {
-  __shared__ float part[3][32][JB + 1];
-
-  const int wg = blockIdx.x;
-  const int wave = threadIdx.x / NATS_WAVE;
-  const int m = wave / 3;
-  const int ks = wave % 3;
-  const int i0 = wg * JB;
-
-  const int kchunk = ((Kpad / 3 + 31) / 32) * 32;
-  const int kbeg = ks * kchunk;
-  const int kend = min(Kpad, (ks + 1) * kchunk);
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  NATS_MFMA_KLOOP(acc, dstep, 16 * m, Kpad, Wt, i0, Kpad, kbeg, kend);
-  store_cd_lds(part[ks], acc, 16 * m);
-  __syncthreads();
-
-  for (int idx = threadIdx.x; idx < B * JB; idx += blockDim.x) {
-    const int b = idx / JB;
-    const int c = idx % JB;
-    const int i = i0 + c;
-    if (i >= H) continue;
-    out[(long)b * H + i] = ddirect[(long)b * H + i] + part[0][b][c] +
-                           part[1][b][c] + part[2][b][c];
-  }
+  row_gemm(dstep, Wt, blockIdx.x * JB, Kpad, KRange{0, Kpad}, B, H,
+           [&](int b, int i, float sum) {
+             out[(long)b * H + i] = ddirect[(long)b * H + i] + sum;
+           });
 }
 
-
 // ---------------- host drivers ----------------
+
+// entry checks of the forward / backward scans (one direction's tensors)
+static void check_scan_fwd_args(const torch::Tensor& xg,
+                                const torch::Tensor& xc,
+                                const torch::Tensor& Upk) {
+  check_scan_input(xg, torch::kBFloat16, "gru_scan xg");
+  check_scan_input(xc, torch::kBFloat16, "gru_scan xc");
+  TORCH_CHECK(xg.size(2) == 2 * xc.size(2));
+  check_packed_weight(Upk, xc.size(2), 3, "gru_scan Upk");
+}
+
+static void check_scan_bwd_args(const torch::Tensor& dh_out,
+                                const torch::Tensor& saved,
+                                const torch::Tensor& xc,
+                                const torch::Tensor& Ubwd) {
+  check_scan_input(dh_out, torch::kFloat32, "gru_scan dh_out");
+  check_scan_input(saved, torch::kBFloat16, "gru_scan saved");
+  check_scan_input(xc, torch::kBFloat16, "gru_scan xc");
+  check_packed_weight(Ubwd, dh_out.size(2), 1, "gru_scan Ubwd");
+}
 
 std::vector<torch::Tensor> gru_scan_fwd(torch::Tensor xg, torch::Tensor xc,
                                         c10::optional<torch::Tensor> mask,
                                         torch::Tensor Upk,
                                         c10::optional<torch::Tensor> h0) {
-  TORCH_CHECK(xg.is_cuda() && xg.dtype() == torch::kBFloat16 &&
-              xg.is_contiguous());
-  TORCH_CHECK(xc.is_cuda() && xc.dtype() == torch::kBFloat16 &&
-              xc.is_contiguous());
+  check_scan_fwd_args(xg, xc, Upk);
   const int T = xg.size(0), B = xg.size(1), H = xc.size(2);
-  TORCH_CHECK(xg.size(2) == 2 * H);
   TORCH_CHECK(B <= 32, "gru_scan: batch per step must be <= 32 (got ", B,
               "); use more DP ranks or smaller micro-batches");
   const int Hpad = Upk.size(1);
   const int ngrp = cdiv(H, JB);
-  TORCH_CHECK(Upk.size(0) == ngrp * 3 * JB && Upk.is_contiguous());
 
   auto optsF = xg.options().dtype(torch::kFloat32);
   auto optsB = xg.options();
   auto h_all = torch::empty({T, B, H}, optsF);
   auto saved = torch::empty({T, B, 3 * H}, optsB);
-  auto h_bf = torch::zeros({2, 32, Hpad}, optsB);
+  auto h_bf = torch::zeros({2, 32, Hpad}, optsB);  // ping-pong
   torch::Tensor hprev0;
   if (h0.has_value()) {
     hprev0 = h0->contiguous().to(torch::kFloat32);
@@ -890,27 +687,19 @@ std::vector<torch::Tensor> gru_scan_fwd(torch::Tensor xg, torch::Tensor xc,
     hprev0 = torch::zeros({B, H}, optsF);
   }
   const OptF32 mask_f(mask);
-  const float* mask_p = mask_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  const bf16_t* xg_p = (const bf16_t*)xg.data_ptr();
-  const bf16_t* xc_p = (const bf16_t*)xc.data_ptr();
-  float* h_all_p = h_all.data_ptr<float>();
-  bf16_t* saved_p = (bf16_t*)saved.data_ptr();
-  bf16_t* hbf_p = (bf16_t*)h_bf.data_ptr();
-  const bf16_t* Upk_p = (const bf16_t*)Upk.data_ptr();
-  const float* h0_p = hprev0.data_ptr<float>();
-
-  const long hbuf_stride = (long)32 * Hpad;
+  const Steps<const bf16_t> xg_s(xg), xc_s(xc);
+  const Steps<const float> mask_s(mask_f.t);
+  const Steps<float> h_s(h_all);
+  const Steps<bf16_t> saved_s(saved), hbf_s(h_bf);
   for (int t = 0; t < T; ++t) {
-    const float* hprev = (t == 0) ? h0_p : (h_all_p + (long)(t - 1) * B * H);
     hipLaunchKernelGGL(nats_gru_step_fwd, dim3(ngrp), dim3(384), 0, stream,
-                       hbf_p + (t % 2) * hbuf_stride, hprev, Upk_p,
-                       xg_p + (long)t * B * 2 * H, xc_p + (long)t * B * H,
-                       mask_p ? mask_p + (long)t * B : nullptr,
-                       h_all_p + (long)t * B * H,
-                       hbf_p + ((t + 1) % 2) * hbuf_stride, Hpad,
-                       saved_p + (long)t * B * 3 * H, B, H, Hpad);
+                       hbf_s.at(t % 2),
+                       t == 0 ? hprev0.data_ptr<float>() : h_s.at(t - 1),
+                       (const bf16_t*)Upk.data_ptr(), xg_s.at(t), xc_s.at(t),
+                       mask_s.at(t), h_s.at(t), hbf_s.at((t + 1) % 2), Hpad,
+                       saved_s.at(t), B, H, Hpad);
   }
   HIP_CHECK(hipGetLastError());
   return {h_all, saved};
@@ -921,6 +710,9 @@ std::vector<torch::Tensor> gru_scan_fwd(torch::Tensor xg, torch::Tensor xc,
 // slot needs a block of its own, all resident at once.
 constexpr int NATS_PERSIST_GRID = 256;
 constexpr size_t NATS_PERSIST_SMEM_MAX = 150 * 1024;  // >= 1 block per CU
+constexpr int NATS_PERSIST_MAX_JOBS = 4;
+// per-job claim counters, after the jobs' barrier slabs in the sync tensor
+constexpr int NATS_CLAIM_WORDS = 8;
 
 // The one place that decides whether (H, B) runs on the persistent scans
 // and with which geometry: jobs = directions x 32-row batch chunks
@@ -943,10 +735,16 @@ static GruPersistPlan gru_persist_plan(int H, int B) {
   p.smem_bwd = JB * K3pad * 2 + tiles;     // [16][K3pad] bf16 + part
   // 2 XCDs (64 CUs) per job when its grid fits comfortably (LCSTS
   // ngrp=32: +2.5% measured); 4 when 63 WGs would sit 1/CU
-  const char* xpd_env = getenv("NATS_XPD");
-  p.xpd = xpd_env ? atoi(xpd_env)
-                  : (p.njobs == 4 ? 2 : (p.ngrp <= 48 ? 2 : 4));
-  p.ok = p.njobs <= 4 && 2 * p.ngrp <= 192 &&
+  p.xpd = p.njobs == 4 ? 2 : (p.ngrp <= 48 ? 2 : 4);
+  if (const char* xpd_env = getenv("NATS_XPD")) {
+    // the claim divides an XCC id by it: 0 or garbage must not get there
+    char* end = nullptr;
+    const long v = strtol(xpd_env, &end, 10);
+    TORCH_CHECK(end != xpd_env && *end == '\0' && v >= 1 && v <= 8,
+                "NATS_XPD must be an integer in [1, 8], got '", xpd_env, "'");
+    p.xpd = (int)v;
+  }
+  p.ok = p.njobs <= NATS_PERSIST_MAX_JOBS && 2 * p.ngrp <= 192 &&
          p.njobs * p.ngrp <= NATS_PERSIST_GRID &&
          p.smem_fwd <= NATS_PERSIST_SMEM_MAX &&
          p.smem_bwd <= NATS_PERSIST_SMEM_MAX &&
@@ -959,6 +757,21 @@ bool gru_persistent_ok(long H, long B) {
   return gru_persist_plan((int)H, (int)B).ok;
 }
 
+// Job j of a bidirectional scan -> direction d, first batch row a, rows;
+// directions interleave so one direction's chunk pairs sit on far XCD sets.
+// The per-step path runs jobs 0 and 1 (one per direction, all rows).
+struct GruJob { int d, a, rows; };
+static GruJob gru_job(int j, int B) {
+  const int a = (j >> 1) * 32;
+  return GruJob{j & 1, a, std::min(32, B - a)};
+}
+
+// zeroed sync tensor of a launch: a barrier slab per job, then the claims
+static torch::Tensor persist_sync(int njobs, const torch::Tensor& like) {
+  return torch::zeros({njobs * NATS_SYNC_WORDS + NATS_CLAIM_WORDS},
+                      like.options().dtype(torch::kInt32));
+}
+
 // Bidirectional encoder forward: the persistent launch when the plan
 // allows it, else one launch per timestep covering both directions
 // (grid.y = direction). h0 = 0 (nats.py:360).
@@ -966,6 +779,8 @@ std::vector<torch::Tensor> gru_scan_fwd_bidir(
     torch::Tensor xg0, torch::Tensor xc0, c10::optional<torch::Tensor> mask0,
     torch::Tensor Upk0, torch::Tensor xg1, torch::Tensor xc1,
     c10::optional<torch::Tensor> mask1, torch::Tensor Upk1) {
+  check_scan_fwd_args(xg0, xc0, Upk0);
+  check_scan_fwd_args(xg1, xc1, Upk1);
   const int T = xg0.size(0), B = xg0.size(1), H = xc0.size(2);
   TORCH_CHECK(B <= 64, "bidir gru_scan: batch must be <= 64");
   const int Hpad = Upk0.size(1);
@@ -975,7 +790,8 @@ std::vector<torch::Tensor> gru_scan_fwd_bidir(
   auto optsF = xg0.options().dtype(torch::kFloat32);
   auto optsB = xg0.options();
   const torch::Tensor xg[2] = {xg0, xg1}, xc[2] = {xc0, xc1};
-  const torch::Tensor Upk[2] = {Upk0, Upk1};
+  const bf16_t* Upk[2] = {(const bf16_t*)Upk0.data_ptr(),
+                          (const bf16_t*)Upk1.data_ptr()};
   const OptF32 mask[2] = {OptF32(mask0), OptF32(mask1)};
   torch::Tensor h_all[2], saved[2];
   for (int d = 0; d < 2; ++d) {
@@ -983,40 +799,36 @@ std::vector<torch::Tensor> gru_scan_fwd_bidir(
     saved[d] = torch::empty({T, B, 3 * H}, optsB);
   }
   auto h00 = torch::zeros({B, H}, optsF);
+  const Steps<float> h00_rows(h00);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  const long hb = (long)32 * Hpad;
 
   if (plan.ok) {  // weight slices LDS-resident across all T steps
     const int njobs = plan.njobs;
-    auto sync = torch::zeros({njobs * NATS_SYNC_WORDS + 8},
-                             xg0.options().dtype(torch::kInt32));
+    auto sync = persist_sync(njobs, xg0);
     auto h_bfj = torch::zeros({njobs, 2, 32, Hpad}, optsB);
-    GruPersistFwd jobs[4];
+    const Steps<bf16_t> hbf_jobs(h_bfj);
+    GruPersistFwd jobs[NATS_PERSIST_MAX_JOBS];
     for (int j = 0; j < njobs; ++j) {
-      const int d = j & 1;         // interleave so chunk pairs of a
-      const int a = (j >> 1) * 32; // direction sit on far XCD sets
+      const GruJob jb = gru_job(j, B);
+      const int d = jb.d;
+      const Steps<const bf16_t> xg_s(xg[d], jb.a), xc_s(xc[d], jb.a);
+      const Steps<const float> mask_s(mask[d].t, jb.a);
+      const Steps<float> h_s(h_all[d], jb.a);
+      const Steps<bf16_t> saved_s(saved[d], jb.a);
       jobs[j] = GruPersistFwd{
-          (const bf16_t*)xg[d].data_ptr() + (long)a * 2 * H,
-          (const bf16_t*)xc[d].data_ptr() + (long)a * H,
-          mask[d].p ? mask[d].p + a : nullptr,
-          (const bf16_t*)Upk[d].data_ptr(),
-          h_all[d].data_ptr<float>() + (long)a * H,
-          (bf16_t*)h_bfj.data_ptr() + (long)j * 2 * hb,
-          (bf16_t*)saved[d].data_ptr() + (long)a * 3 * H,
-          h00.data_ptr<float>() + (long)a * H,
-          std::min(32, B - a),
-          (long)B * 2 * H, (long)B * H, (long)B, (long)B * H,
-          (long)B * 3 * H};
+          xg_s.base, xc_s.base, mask_s.base, Upk[d], h_s.base,
+          hbf_jobs.at(j), saved_s.base, h00_rows.at(jb.a), jb.rows,
+          xg_s.stride, xc_s.stride, mask_s.stride, h_s.stride,
+          saved_s.stride};
     }
-    for (int j = njobs; j < 4; ++j) jobs[j] = jobs[0];
-    const int unsafe = getenv("NATS_UNSAFE_NOBARRIER") != nullptr;
+    for (int j = njobs; j < NATS_PERSIST_MAX_JOBS; ++j) jobs[j] = jobs[0];
     // overprovisioned 1-D grid: blocks self-select a (job, tile) slot
     // with XCD preference (see nats_claim_job_slot)
     hipLaunchKernelGGL(nats_gru_persistent_fwd, dim3(NATS_PERSIST_GRID),
                        dim3(384), plan.smem_fwd, stream, jobs[0], jobs[1],
                        jobs[2], jobs[3], T, H, Hpad,
-                       (unsigned*)sync.data_ptr<int>(), ngrp, njobs, plan.xpd,
-                       unsafe);
+                       (unsigned*)sync.data_ptr<int>(), ngrp, njobs,
+                       plan.xpd);
     HIP_CHECK(hipGetLastError());
     return {h_all[0], saved[0], h_all[1], saved[1]};
   }
@@ -1024,21 +836,17 @@ std::vector<torch::Tensor> gru_scan_fwd_bidir(
   TORCH_CHECK(B <= 32,
               "bidir scan: B > 32 requires the persistent path "
               "(gru_persistent_ok)");
-  auto h_bf = torch::zeros({2, 2, 32, Hpad}, optsB);  // [dir][pingpong]
-  bf16_t* hbf = (bf16_t*)h_bf.data_ptr();
+  auto h_bf = torch::zeros({2 * 2, 32, Hpad}, optsB);  // [dir][pingpong]
+  const Steps<bf16_t> hbf_s(h_bf);
   for (int t = 0; t < T; ++t) {
     auto args = [&](int d) {
-      float* h = h_all[d].data_ptr<float>();
+      const Steps<float> h_s(h_all[d]);
       return GruFwdArgs{
-          hbf + (2 * d + t % 2) * hb,
-          (t == 0) ? h00.data_ptr<float>() : h + (long)(t - 1) * B * H,
-          (const bf16_t*)Upk[d].data_ptr(),
-          (const bf16_t*)xg[d].data_ptr() + (long)t * B * 2 * H,
-          (const bf16_t*)xc[d].data_ptr() + (long)t * B * H,
-          mask[d].p ? mask[d].p + (long)t * B : nullptr,
-          h + (long)t * B * H,
-          hbf + (2 * d + (t + 1) % 2) * hb,
-          (bf16_t*)saved[d].data_ptr() + (long)t * B * 3 * H};
+          hbf_s.at(2 * d + t % 2), t == 0 ? h00_rows.base : h_s.at(t - 1),
+          Upk[d], Steps<const bf16_t>(xg[d]).at(t),
+          Steps<const bf16_t>(xc[d]).at(t),
+          Steps<const float>(mask[d].t).at(t), h_s.at(t),
+          hbf_s.at(2 * d + (t + 1) % 2), Steps<bf16_t>(saved[d]).at(t)};
     };
     hipLaunchKernelGGL(nats_gru_step_fwd_bidir, dim3(ngrp, 2), dim3(384), 0,
                        stream, args(0), args(1), Hpad, B, H, Hpad);
@@ -1056,6 +864,8 @@ std::vector<torch::Tensor> gru_scan_bwd_bidir(
     torch::Tensor Ubwd0, torch::Tensor dh_out1, torch::Tensor h_all1,
     torch::Tensor saved1, torch::Tensor xc1,
     c10::optional<torch::Tensor> mask1, torch::Tensor Ubwd1) {
+  check_scan_bwd_args(dh_out0, saved0, xc0, Ubwd0);
+  check_scan_bwd_args(dh_out1, saved1, xc1, Ubwd1);
   const int T = dh_out0.size(0), B = dh_out0.size(1), H = dh_out0.size(2);
   const int K3pad = Ubwd0.size(1);
   const GruPersistPlan plan = gru_persist_plan(H, B);
@@ -1063,10 +873,11 @@ std::vector<torch::Tensor> gru_scan_bwd_bidir(
 
   auto optsF = dh_out0.options();
   auto optsB = dh_out0.options().dtype(torch::kBFloat16);
+  const torch::Tensor dh_out[2] = {dh_out0, dh_out1};
   const torch::Tensor h_all[2] = {h_all0, h_all1}, saved[2] = {saved0, saved1};
-  const torch::Tensor xc[2] = {xc0, xc1}, Ubwd[2] = {Ubwd0, Ubwd1};
-  const torch::Tensor dhc[2] = {dh_out0.contiguous().to(torch::kFloat32),
-                                dh_out1.contiguous().to(torch::kFloat32)};
+  const torch::Tensor xc[2] = {xc0, xc1};
+  const bf16_t* Ubwd[2] = {(const bf16_t*)Ubwd0.data_ptr(),
+                           (const bf16_t*)Ubwd1.data_ptr()};
   const OptF32 mask[2] = {OptF32(mask0), OptF32(mask1)};
   torch::Tensor dpre[2], dh0[2];
   for (int d = 0; d < 2; ++d) {
@@ -1074,42 +885,35 @@ std::vector<torch::Tensor> gru_scan_bwd_bidir(
     dh0[d] = torch::empty({B, H}, optsF);
   }
   auto h00 = torch::zeros({B, H}, optsF);
+  const Steps<const float> h00_rows(h00);
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  const long ds = (long)32 * K3pad;
 
   // one job per (direction, 32-row chunk) on the persistent path, one per
   // direction on the per-step path; each owns a dstep ping-pong pair and a
-  // ddirect slab of ddstride floats
+  // ddirect slab
   const int njobs = plan.ok ? plan.njobs : 2;
-  const long ddstride = plan.ok ? (long)32 * H : (long)B * H;
-  auto dstep = torch::zeros({njobs, 2, 32, K3pad}, optsB);
-  auto ddir = torch::zeros({njobs * ddstride}, optsF);
-  bf16_t* dsp = (bf16_t*)dstep.data_ptr();
-  float* dd = ddir.data_ptr<float>();
+  auto dstep = torch::zeros({njobs * 2, 32, K3pad}, optsB);  // [job][pingpong]
+  auto ddir = torch::zeros({njobs, (plan.ok ? 32 : B) * H}, optsF);
+  const Steps<bf16_t> dstep_s(dstep);
+  const Steps<float> ddir_s(ddir);
 
   if (plan.ok) {
-    auto sync = torch::zeros({njobs * NATS_SYNC_WORDS + 8},
-                             dh_out0.options().dtype(torch::kInt32));
-    GruPersistBwd jobs[4];
+    auto sync = persist_sync(njobs, dh_out0);
+    GruPersistBwd jobs[NATS_PERSIST_MAX_JOBS];
     for (int j = 0; j < njobs; ++j) {
-      const int d = j & 1;
-      const int a = (j >> 1) * 32;
+      const GruJob jb = gru_job(j, B);
+      const int d = jb.d;
+      const Steps<const float> dh_s(dh_out[d], jb.a), h_s(h_all[d], jb.a);
+      const Steps<const bf16_t> saved_s(saved[d], jb.a), xc_s(xc[d], jb.a);
+      const Steps<const float> mask_s(mask[d].t, jb.a);
+      const Steps<bf16_t> dpre_s(dpre[d], jb.a);
       jobs[j] = GruPersistBwd{
-          dhc[d].data_ptr<float>() + (long)a * H,
-          h_all[d].data_ptr<float>() + (long)a * H,
-          (const bf16_t*)saved[d].data_ptr() + (long)a * 3 * H,
-          (const bf16_t*)xc[d].data_ptr() + (long)a * H,
-          mask[d].p ? mask[d].p + a : nullptr,
-          (const bf16_t*)Ubwd[d].data_ptr(),
-          dsp + (long)j * 2 * ds,
-          dd + j * ddstride,
-          (bf16_t*)dpre[d].data_ptr() + (long)a * 4 * H,
-          h00.data_ptr<float>() + (long)a * H,
-          std::min(32, B - a),
-          (long)B * H, (long)B * H, (long)B * 3 * H, (long)B * H,
-          (long)B, (long)B * 4 * H};
+          dh_s.base, h_s.base, saved_s.base, xc_s.base, mask_s.base, Ubwd[d],
+          dstep_s.at(2 * j), ddir_s.at(j), dpre_s.base, h00_rows.at(jb.a),
+          jb.rows, dh_s.stride, h_s.stride, saved_s.stride, xc_s.stride,
+          mask_s.stride, dpre_s.stride};
     }
-    for (int j = njobs; j < 4; ++j) jobs[j] = jobs[0];
+    for (int j = njobs; j < NATS_PERSIST_MAX_JOBS; ++j) jobs[j] = jobs[0];
     hipLaunchKernelGGL(nats_gru_persistent_bwd, dim3(NATS_PERSIST_GRID),
                        dim3(384), plan.smem_bwd, stream, jobs[0], jobs[1],
                        jobs[2], jobs[3], T, H, K3pad,
@@ -1123,34 +927,26 @@ std::vector<torch::Tensor> gru_scan_bwd_bidir(
       // parity: step t reads dstep[(t+1)%2], writes dstep[t%2]
       auto args = [&](int d) {
         return GruBwdArgs{
-            dsp + (2 * d + (t + 1) % 2) * ds,
-            dd + d * ddstride,
-            dhc[d].data_ptr<float>() + (long)t * B * H,
-            (const bf16_t*)saved[d].data_ptr() + (long)t * B * 3 * H,
-            (const bf16_t*)xc[d].data_ptr() + (long)t * B * H,
-            (t == 0) ? h00.data_ptr<float>()
-                     : h_all[d].data_ptr<float>() + (long)(t - 1) * B * H,
-            mask[d].p ? mask[d].p + (long)t * B : nullptr,
-            dsp + (2 * d + t % 2) * ds,
-            dd + d * ddstride,
-            (bf16_t*)dpre[d].data_ptr() + (long)t * B * 4 * H};
+            dstep_s.at(2 * d + (t + 1) % 2), ddir_s.at(d),
+            Steps<const float>(dh_out[d]).at(t),
+            Steps<const bf16_t>(saved[d]).at(t),
+            Steps<const bf16_t>(xc[d]).at(t),
+            t == 0 ? h00_rows.base : Steps<const float>(h_all[d]).at(t - 1),
+            Steps<const float>(mask[d].t).at(t), dstep_s.at(2 * d + t % 2),
+            ddir_s.at(d), Steps<bf16_t>(dpre[d]).at(t)};
       };
       hipLaunchKernelGGL(nats_gru_step_bwd_fused_bidir, dim3(ngrp, 2),
-                         dim3(384), 0, stream, args(0), args(1),
-                         (const bf16_t*)Ubwd[0].data_ptr(),
-                         (const bf16_t*)Ubwd[1].data_ptr(), B, H, K3pad);
+                         dim3(384), 0, stream, args(0), args(1), Ubwd[0],
+                         Ubwd[1], B, H, K3pad);
     }
   }
   // final dh0 per job (dstep(0) lives in ping-pong slot 0); each job
   // writes its chunk's rows of the (B,H) dh0 output
   for (int j = 0; j < njobs; ++j) {
-    const int d = j & 1;
-    const int a = (j >> 1) * 32;
+    const GruJob jb = gru_job(j, B);
     hipLaunchKernelGGL(nats_gru_step_bwd_gemm, dim3(ngrp), dim3(384), 0,
-                       stream, dsp + (long)j * 2 * ds,
-                       (const bf16_t*)Ubwd[d].data_ptr(), dd + j * ddstride,
-                       dh0[d].data_ptr<float>() + (long)a * H,
-                       std::min(32, B - a), H, K3pad);
+                       stream, dstep_s.at(2 * j), Ubwd[jb.d], ddir_s.at(j),
+                       Steps<float>(dh0[jb.d]).at(jb.a), jb.rows, H, K3pad);
   }
   HIP_CHECK(hipGetLastError());
   return {dpre[0], dh0[0], dpre[1], dh0[1]};
@@ -1162,14 +958,10 @@ std::vector<torch::Tensor> gru_scan_bwd(torch::Tensor dh_out,
                                         c10::optional<torch::Tensor> mask,
                                         torch::Tensor Ubwd,
                                         c10::optional<torch::Tensor> h0) {
-  TORCH_CHECK(dh_out.is_cuda() && dh_out.dtype() == torch::kFloat32 &&
-              dh_out.is_contiguous());
+  check_scan_bwd_args(dh_out, saved, xc, Ubwd);
   const int T = dh_out.size(0), B = dh_out.size(1), H = dh_out.size(2);
   const int K3pad = Ubwd.size(1);
   const int ngrp = cdiv(H, JB);
-  TORCH_CHECK(Ubwd.size(0) == ngrp * JB && Ubwd.is_contiguous());
-  TORCH_CHECK(saved.dtype() == torch::kBFloat16 &&
-              xc.dtype() == torch::kBFloat16);
 
   auto optsF = dh_out.options();
   auto optsB = dh_out.options().dtype(torch::kBFloat16);
@@ -1181,142 +973,28 @@ std::vector<torch::Tensor> gru_scan_bwd(torch::Tensor dh_out,
                              ? h0->contiguous().to(torch::kFloat32)
                              : torch::zeros({B, H}, optsF);
   const OptF32 mask_f(mask);
-  const float* mask_p = mask_f.p;
 
   auto stream = at::cuda::getCurrentCUDAStream().stream();
-  const float* dh_out_p = dh_out.data_ptr<float>();
-  const float* h_all_p = h_all.data_ptr<float>();
-  const bf16_t* saved_p = (const bf16_t*)saved.data_ptr();
-  const bf16_t* xc_p = (const bf16_t*)xc.data_ptr();
-  bf16_t* dpre_p = (bf16_t*)dpre_all.data_ptr();
+  const Steps<const float> dh_s(dh_out), h_s(h_all), mask_s(mask_f.t);
+  const Steps<const bf16_t> saved_s(saved), xc_s(xc);
+  const Steps<bf16_t> dpre_s(dpre_all);
   float* dh_buf_p = dh_buf.data_ptr<float>();
   float* ddirect_p = ddirect.data_ptr<float>();
   bf16_t* dstep_p = (bf16_t*)dstep.data_ptr();
-  const bf16_t* Ubwd_p = (const bf16_t*)Ubwd.data_ptr();
 
   const int pw_blocks = (int)std::min<long>(1024, (((long)B * H) + 255) / 256);
   for (int t = T - 1; t >= 0; --t) {
-    const float* hprev = (t == 0) ? hprev0.data_ptr<float>()
-                                  : (h_all_p + (long)(t - 1) * B * H);
     hipLaunchKernelGGL(nats_gru_step_bwd_pointwise, dim3(pw_blocks), dim3(256),
-                       0, stream, dh_buf_p, dh_out_p + (long)t * B * H,
-                       saved_p + (long)t * B * 3 * H, xc_p + (long)t * B * H,
-                       hprev, mask_p ? mask_p + (long)t * B : nullptr, dstep_p,
-                       K3pad, ddirect_p, dpre_p + (long)t * B * 4 * H, B, H);
+                       0, stream, dh_buf_p, dh_s.at(t), saved_s.at(t),
+                       xc_s.at(t),
+                       t == 0 ? hprev0.data_ptr<float>() : h_s.at(t - 1),
+                       mask_s.at(t), dstep_p, K3pad, ddirect_p, dpre_s.at(t),
+                       B, H);
     hipLaunchKernelGGL(nats_gru_step_bwd_gemm, dim3(ngrp), dim3(384), 0,
-                       stream, dstep_p, Ubwd_p, ddirect_p, dh_buf_p, B, H,
-                       K3pad);
+                       stream, dstep_p, (const bf16_t*)Ubwd.data_ptr(),
+                       ddirect_p, dh_buf_p, B, H, K3pad);
   }
   HIP_CHECK(hipGetLastError());
   return {dpre_all, dh_buf};
 }
 
-
-// ---- grid-barrier micro-benchmark: isolates the per-step sync cost of
-// the persistent scans (timing evidence in profiles/README.md). ----
-__global__ __launch_bounds__(384) void nats_barrier_bench_kernel(
-    unsigned* sync, unsigned nwg, int iters, float* out) {
-  NatsBarrierCtx bctx;
-  if (!nats_barrier_init(sync, nwg, bctx)) return;
-  for (int t = 0; t < iters; ++t) {
-    if (!nats_grid_barrier(sync, (unsigned)(t + 1), bctx)) return;
-  }
-  if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) out[0] = 1.f;
-}
-
-// XCD-constrained variant: measures whether co-locating all
-// participants on few XCDs cuts the barrier floor (candidate fix for
-// the encoder persistent-scan sync floor — VERDICT r1 weak #1). Launch
-// overprovisions blocks; a census picks exactly `nwg` participants that
-// sit on XCDs with id < nxcd; everyone else exits. Extra sync words
-// beyond NATS_SYNC_WORDS: [W+0..W+7] census per XCD, [W+8] census total,
-// [W+9] participant slot counter, [W+10] participants-found flag.
-__global__ __launch_bounds__(384) void nats_barrier_bench_xcd_kernel(
-    unsigned* sync, unsigned nwg, unsigned nxcd, unsigned launched,
-    int iters, float* out) {
-  constexpr int W = NATS_SYNC_WORDS;
-  __shared__ int role;  // 0 = exit, 1 = participate
-  if (threadIdx.x == 0) {
-    const unsigned xcc = nats_xcc_id();
-    __hip_atomic_fetch_add(sync + W + xcc, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(sync + W + 8, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    while (__hip_atomic_load(sync + W + 8, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT) < launched &&
-           ++spins < 200000000u)
-      __builtin_amdgcn_s_sleep(2);
-    int take = 0;
-    if (xcc < nxcd) {
-      const unsigned slot = __hip_atomic_fetch_add(
-          sync + W + 9, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      take = (slot < nwg);
-    }
-    role = take;
-  }
-  __syncthreads();
-  if (!role) return;
-
-  NatsBarrierCtx bctx;
-  if (!nats_barrier_init(sync, nwg, bctx)) return;
-  for (int t = 0; t < iters; ++t) {
-    if (!nats_grid_barrier(sync, (unsigned)(t + 1), bctx)) return;
-  }
-  if (threadIdx.x == 0)
-    __hip_atomic_store(sync + W + 10, 1u, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = 1.f;
-}
-
-double barrier_bench_xcd(int nwg, int nxcd, int iters) {
-  auto opts = torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA);
-  auto sync = torch::zeros({NATS_SYNC_WORDS + 12}, opts);
-  auto out = torch::zeros(
-      {1}, torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  // overprovision so the target XCDs hold >= nwg blocks after round-robin
-  // dispatch (256 CUs / 8 XCDs; 2 blocks per CU fit at 384 threads)
-  const unsigned launched =
-      (unsigned)std::min(512, std::max(8 * ((nwg + nxcd - 1) / nxcd), 64));
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  HIP_CHECK(hipEventRecord(e0, stream));
-  hipLaunchKernelGGL(nats_barrier_bench_xcd_kernel, dim3(launched), dim3(384),
-                     0, stream, (unsigned*)sync.data_ptr<int>(),
-                     (unsigned)nwg, (unsigned)nxcd, launched, iters,
-                     out.data_ptr<float>());
-  HIP_CHECK(hipEventRecord(e1, stream));
-  HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  TORCH_CHECK(sync[NATS_SYNC_WORDS + 10].item<int>() == 1,
-              "xcd barrier bench gave up");
-  return (double)ms * 1000.0 / iters;  // us per barrier (incl. census)
-}
-
-double barrier_bench(int nwg_x, int nwg_y, int iters) {
-  auto opts = torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA);
-  auto sync = torch::zeros({NATS_SYNC_WORDS}, opts);
-  auto out = torch::zeros(
-      {1}, torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  HIP_CHECK(hipEventRecord(e0, stream));
-  hipLaunchKernelGGL(nats_barrier_bench_kernel, dim3(nwg_x, nwg_y), dim3(384),
-                     0, stream, (unsigned*)sync.data_ptr<int>(),
-                     (unsigned)(nwg_x * nwg_y), iters, out.data_ptr<float>());
-  HIP_CHECK(hipEventRecord(e1, stream));
-  HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  TORCH_CHECK(out.item<float>() == 1.f, "barrier bench gave up");
-  return (double)ms * 1000.0 / iters;  // us per barrier
-}

@@ -316,6 +316,19 @@ def test_gru_persistent_plan_truth_table(ext, H, B, expected):
     assert ext.gru_persistent_ok(H, B) is expected
 
 
+def test_gru_persistent_plan_rejects_bad_xpd(ext, monkeypatch):
+    """Host-only: NATS_XPD (preferred XCDs per job) divides an XCC id in the
+    claim, so anything but an integer in [1, 8] must raise, naming the
+    variable; a valid value leaves the answer as without it."""
+    expected = ext.gru_persistent_ok(1000, 20)
+    for bad in ("0", "9", "two"):
+        monkeypatch.setenv("NATS_XPD", bad)
+        with pytest.raises(RuntimeError, match="NATS_XPD"):
+            ext.gru_persistent_ok(1000, 20)
+    monkeypatch.setenv("NATS_XPD", "2")
+    assert ext.gru_persistent_ok(1000, 20) is expected
+
+
 def test_gru_scan_bidir_wide_hidden_large_batch(ext):
     """B > 32 with H in (1024, 1504]: four persistent jobs would need more
     claim slots than the grid has blocks, so the dispatcher must take the

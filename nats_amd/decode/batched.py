@@ -16,7 +16,10 @@ the alignment output (two small synchronisations per step — the naive
 numpy bookkeeping round-trip was ~25% of decode time in the kernel
 trace, profiles/decode_kernel_stats.csv). With ``fused_select=True`` the
 per-sentence top-k loop becomes one ops.beam_select call per step
-(measured in profiles/README.md, "Decode v4").
+(measured in profiles/README.md, "Decode v4"). With ``paged_rerank=True``
+the rerank histories of all sentences live in one ops.RerankHistory: each
+step's rows are stored once and an int32 ancestor table is reshuffled
+instead of the histories themselves (docs/DESIGN.md, "Rerank histories").
 
 Numerics note: results are mathematically identical to per-sentence
 gen_sample, but not bitwise — the batched masked-mean init state and
@@ -36,7 +39,8 @@ from .beam import distraction_penalties_gpu
 
 
 def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
-                  any_lambda, kl_factor, ctx_factor, state_factor):
+                  any_lambda, kl_factor, ctx_factor, state_factor,
+                  paged_pen=None):
     """Phases 1 and 2a of a decode step through ops.beam_select: one upload
     ([running scores | seg_off | want], the fp32 scores carried as their
     int32 bits), one selection call for every alive sentence, one copy of
@@ -44,7 +48,9 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
 
     Returns (pend, alpha_sel) exactly as the per-sentence path builds
     them: pend[j] = (i, sl, tis, wis, costs, sel_dev) per alive sentence,
-    alpha_sel the selected attention rows in pend order (host array)."""
+    alpha_sel the selected attention rows in pend order (host array).
+    ``paged_pen``: the (R,) rerank penalties of a RerankHistory, used in
+    place of the per-sentence ones."""
     device = probs.device
     V = probs.shape[1]
     lives = [st[i]["live"] for i in alive]
@@ -61,7 +67,9 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
 
     # rerank penalties stay per sentence (zeros where there is no history)
     penalty = None
-    if ii > 0 and any_lambda:
+    if ii > 0 and paged_pen is not None:
+        penalty = paged_pen
+    elif ii > 0 and any_lambda:
         pens = []
         for j, i in enumerate(alive):
             sl = slice(int(seg[j]), int(seg[j + 1]))
@@ -98,13 +106,20 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
 @torch.no_grad()
 def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                        kl_factor=0.0, ctx_factor=0.0, state_factor=0.0,
-                       use_graph=True, fused_select=False):
+                       use_graph=True, fused_select=False,
+                       paged_rerank=False):
     """Beam-decode a list of sources jointly.
 
     fused_select: pick every sentence's candidates with one
     ops.beam_select call per step (one table upload, one result copy)
     instead of the per-sentence topk loop. Same keys; exactly equal keys
     go to the lower flat index (topk leaves that choice open). Opt-in.
+
+    paged_rerank: keep the distraction-rerank histories of all sentences
+    in one ops.RerankHistory (slabs written once per step + an ancestor
+    table) and compute every row's penalties in one call per step, instead
+    of re-gathering dense per-sentence histories. Same penalties bit for
+    bit; a no-op when all three factors are 0. Opt-in.
 
     xs: list of (T_i, 1) int64 tensors (same device as model).
     maxlen: an int, or a per-sentence list (serving: each request brings
@@ -122,6 +137,8 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
     assert len(maxlens) == S
     device = xs[0].device
     any_lambda = (kl_factor > 0.0 or ctx_factor > 0.0 or state_factor > 0.0)
+    paged = bool(paged_rerank) and any_lambda
+    history = None  # ops.RerankHistory, built at the first step
 
     # ONE batched masked encode for all sentences (identical per-column to
     # each sentence's own unpadded encode — see f_init): pads to the
@@ -145,7 +162,9 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
 
     # per-sentence host bookkeeping (sample token lists + scores; identical
     # math to gen_sample) — everything tensor-valued lives on device
-    st = [dict(live=1, dead=0, samples=[[]],
+    # prows (paged rerank): the batch row of this step that each live
+    # hypothesis continues, as host ints
+    st = [dict(live=1, dead=0, samples=[[]], prows=[],
                scores=numpy.zeros(1, dtype="float32"),
                alphas=[[]], out_samples=[], out_scores=[], out_alphas=[])
           for _ in range(S)]
@@ -186,8 +205,16 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
         alive = [i for i in range(S) if st[i]["live"] > 0]
         if not alive:
             break
-        sent_idx = torch.tensor(
-            sum(([i] * st[i]["live"] for i in alive), []), device=device)
+        sent_rows = sum(([i] * st[i]["live"] for i in alive), [])
+        if paged:
+            # the parents of the ancestor-table advance ride along with
+            # sent_idx: one upload for both
+            up = torch.tensor(
+                sent_rows + sum((st[i]["prows"] for i in alive), []),
+                device=device)
+            sent_idx, parent_dev = up[:len(sent_rows)], up[len(sent_rows):]
+        else:
+            sent_idx = torch.tensor(sent_rows, device=device)
         y = torch.cat([dstate[i]["w"] for i in alive])
         state = torch.cat([dstate[i]["state"] for i in alive])
         acc_c = torch.cat([dstate[i]["acc_c"] for i in alive])
@@ -209,10 +236,21 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 sample_draw=False)
         V = probs.shape[1]
 
+        paged_pen = None
+        if paged:
+            if history is None:
+                history = ops.RerankHistory(
+                    max(maxlens), S * k, alpha.shape[1], ctx_t.shape[1],
+                    h2.shape[1], device)
+            paged_pen = history.step(
+                parent_dev, alpha.float().contiguous(),
+                ctx_t.float().contiguous(), h2.float().contiguous(),
+                (kl_factor, ctx_factor, state_factor))
+
         if fused_select:
             pend, alpha_sel = _select_fused(
                 st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
-                any_lambda, kl_factor, ctx_factor, state_factor)
+                any_lambda, kl_factor, ctx_factor, state_factor, paged_pen)
         else:
             # -- phase 1: per-sentence top-k ON DEVICE, one host transfer --
             logp = probs.float().log()
@@ -230,7 +268,9 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 cand_flat = cand.flatten()
                 want = k - st[i]["dead"]
                 sel_flat = cand_flat
-                if ii > 0 and any_lambda and dstate[i]["ha"] is not None:
+                if ii > 0 and paged:
+                    sel_flat = (cand + paged_pen[sl, None]).flatten()
+                elif ii > 0 and any_lambda and dstate[i]["ha"] is not None:
                     pen = distraction_penalties_gpu(
                         dstate[i]["ha"], dstate[i]["hc"], dstate[i]["hs"],
                         alpha[sl].float(), ctx_t[sl].float(), h2[sl].float(),
@@ -277,7 +317,7 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 new_words.append(int(wi))
 
             # device histories for the rerank (pre-filter selection order)
-            if any_lambda:
+            if any_lambda and not paged:
                 cur_a = alpha.float()[sel_dev].unsqueeze(0)
                 cur_c = ctx_t.float()[sel_dev].unsqueeze(0)
                 cur_s = h2.float()[sel_dev].unsqueeze(0)
@@ -316,7 +356,9 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 dstate[i]["state"] = h2[sel_keep].float()
                 dstate[i]["acc_c"] = acc_c[sel_keep].float()
                 dstate[i]["acc_a"] = acc_a[sel_keep].float()
-                if any_lambda:
+                if paged:
+                    st[i]["prows"] = [sl.start + int(tis[j]) for j in keep]
+                elif any_lambda:
                     dstate[i]["ha"] = ha[:, kt]
                     dstate[i]["hc"] = hc[:, kt]
                     dstate[i]["hs"] = hs[:, kt]

@@ -78,28 +78,15 @@ def distraction_penalties_gpu(hist_a, hist_c, hist_s, cur_a, cur_c, cur_s,
 
     hist_* are (n_hist, live_k, dim) fp32 device tensors; cur_* (live_k,
     dim). Returns a (live_k,) fp32 tensor of summed penalties."""
-    from nats_amd.ops import _hip_ext
+    from nats_amd.ops import _hip_ext, eager
     ext = _hip_ext()
     if ext is not None and hist_a.is_cuda and hasattr(ext, "rerank_penalties"):
         return ext.rerank_penalties(
             hist_a.contiguous(), hist_c.contiguous(), hist_s.contiguous(),
             cur_a.contiguous(), cur_c.contiguous(), cur_s.contiguous(),
             kl_factor, ctx_factor, state_factor)
-    p = hist_a / hist_a.sum(-1, keepdim=True)
-    q = (cur_a / cur_a.sum(-1, keepdim=True)).unsqueeze(0)
-    logterm = torch.where(p > 0, p * (torch.log(p) - torch.log(q)),
-                          torch.zeros_like(p))
-    a_pen = -kl_factor * logterm.sum(-1).min(dim=0).values
-
-    def cosd(h, c):
-        num = (h * c.unsqueeze(0)).sum(-1)
-        den = h.norm(dim=-1) * c.norm(dim=-1).unsqueeze(0)
-        d = 1.0 - num / den
-        return torch.where(den == 0, torch.zeros_like(d), d)
-
-    c_pen = ctx_factor * cosd(hist_c, cur_c).max(dim=0).values
-    s_pen = state_factor * cosd(hist_s, cur_s).max(dim=0).values
-    return a_pen + c_pen + s_pen
+    return eager.rerank_penalties(hist_a, hist_c, hist_s, cur_a, cur_c, cur_s,
+                                  kl_factor, ctx_factor, state_factor)
 
 
 @torch.no_grad()

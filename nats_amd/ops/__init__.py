@@ -328,3 +328,8 @@ def softmax_xent(logits, targets):
         from .softmax_ce import softmax_xent_hip
         return softmax_xent_hip(logits, targets)
     return eager.softmax_xent(logits, targets)
+
+
+# paged distraction-rerank histories (ops defined next to their container)
+from .rerank import (RerankHistory, rerank_advance,  # noqa: E402,F401
+                     rerank_penalties_paged)

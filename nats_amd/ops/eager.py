@@ -190,3 +190,61 @@ def beam_select(probs, prev_cost, seg_off, want, penalty=None, use_unk=True,
         ranks[s, :wants[s]] = order
         costs[s, :wants[s]] = cand[sl].flatten()[order]
     return ranks, costs
+
+
+def rerank_penalties(hist_a, hist_c, hist_s, cur_a, cur_c, cur_s,
+                     kl_factor, ctx_factor, state_factor):
+    """Distraction rerank penalties (nats.py:981-999), vectorised over
+    (history step, hypothesis): hist_* (n, k, dim), cur_* (k, dim) ->
+    (k,) = -kl_factor * min_t KL(hist_a[t] || cur_a) + ctx_factor * max_t
+    cosine_dist(hist_c[t], cur_c) + state_factor * max_t
+    cosine_dist(hist_s[t], cur_s); KL in scipy's entropy convention (both
+    sides normalised, 0 log 0 = 0), cosine distance 0 at a zero norm."""
+    p = hist_a / hist_a.sum(-1, keepdim=True)
+    q = (cur_a / cur_a.sum(-1, keepdim=True)).unsqueeze(0)
+    logterm = torch.where(p > 0, p * (torch.log(p) - torch.log(q)),
+                          torch.zeros_like(p))
+    a_pen = -kl_factor * logterm.sum(-1).min(dim=0).values
+
+    def cosd(h, c):
+        num = (h * c.unsqueeze(0)).sum(-1)
+        den = h.norm(dim=-1) * c.norm(dim=-1).unsqueeze(0)
+        d = 1.0 - num / den
+        return torch.where(den == 0, torch.zeros_like(d), d)
+
+    c_pen = ctx_factor * cosd(hist_c, cur_c).max(dim=0).values
+    s_pen = state_factor * cosd(hist_s, cur_s).max(dim=0).values
+    return a_pen + c_pen + s_pen
+
+
+def rerank_advance(anc_old, anc_new, parent, n):
+    """Ancestor-table reshuffle of a decode step: row r of the new batch
+    continues row parent[r] of the previous one, so it inherits that row's
+    n-1 earlier slots and gets the parent row itself as the slot of step
+    n-1. Tables are (Tmax, Rmax) int32; writes anc_new[:n, :len(parent)]."""
+    parent = torch.as_tensor(parent, dtype=torch.int64,
+                             device=anc_old.device)
+    R = parent.shape[0]
+    anc_new[:n - 1, :R] = anc_old[:n - 1].index_select(1, parent)
+    anc_new[n - 1, :R] = parent.to(anc_new.dtype)
+    return anc_new
+
+
+def rerank_gather(hist, anc, n, R):
+    """Dense (n, R, dim) history of the R current rows, read from a slab
+    hist (Tmax, Rmax, dim) through the ancestor table."""
+    steps = torch.arange(n, device=hist.device)[:, None]
+    return hist[steps, anc[:n, :R].long()]
+
+
+def rerank_penalties_paged(hist_a, hist_c, hist_s, anc, n, cur_a, cur_c,
+                           cur_s, kl_factor, ctx_factor, state_factor):
+    """rerank_penalties on the histories gathered through ``anc``; zeros
+    when there is no history yet."""
+    R = cur_a.shape[0]
+    if n == 0:
+        return torch.zeros(R, dtype=cur_a.dtype, device=cur_a.device)
+    return rerank_penalties(
+        rerank_gather(hist_a, anc, n, R), rerank_gather(hist_c, anc, n, R),
+        rerank_gather(hist_s, anc, n, R), cur_a, cur_c, cur_s,
+        kl_factor, ctx_factor, state_factor)

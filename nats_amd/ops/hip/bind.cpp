@@ -34,6 +34,15 @@ torch::Tensor rerank_penalties(torch::Tensor hist_a, torch::Tensor hist_c,
                                torch::Tensor hist_s, torch::Tensor cur_a,
                                torch::Tensor cur_c, torch::Tensor cur_s,
                                double kl_f, double ctx_f, double state_f);
+void rerank_advance(torch::Tensor anc_old, torch::Tensor anc_new,
+                    torch::Tensor parent, long n);
+torch::Tensor rerank_penalties_paged(torch::Tensor hist_a,
+                                     torch::Tensor hist_c,
+                                     torch::Tensor hist_s, torch::Tensor anc,
+                                     long n, torch::Tensor cur_a,
+                                     torch::Tensor cur_c, torch::Tensor cur_s,
+                                     double kl_f, double ctx_f,
+                                     double state_f);
 std::vector<torch::Tensor> beam_select(torch::Tensor probs,
                                        torch::Tensor prev_cost,
                                        torch::Tensor seg_off,
@@ -105,6 +114,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "XCD-constrained grid barrier us/iteration");
   m.def("rerank_penalties", &rerank_penalties,
         "fused decode-time distraction rerank reductions");
+  m.def("rerank_advance", &rerank_advance,
+        "ancestor-table reshuffle of the paged rerank histories");
+  m.def("rerank_penalties_paged", &rerank_penalties_paged,
+        "rerank reductions over slab histories read through the ancestor "
+        "table (partial pass + combine pass)");
   m.def("beam_select", &beam_select,
         "segmented beam candidate selection (tile pass + merge pass)");
   m.def("fused_adadelta_step", &fused_adadelta_step,

@@ -38,13 +38,16 @@ class SummarizerService:
     batches of up to ``max_batch`` (default: 64 // k beam rows fit the
     kernel launch), waiting at most ``max_wait_ms`` for co-batchable
     requests once one is pending. ``fused_select`` picks each step's beam
-    candidates with one ops.beam_select call (gen_sample_batched).
+    candidates with one ops.beam_select call, ``paged_rerank`` keeps the
+    distraction-rerank histories in one ops.RerankHistory (both
+    gen_sample_batched options, off by default).
     """
 
     def __init__(self, model_path, dictionary, device=None, k=10, maxlen=100,
                  normalize=True, kl_factor=0.0, ctx_factor=0.0,
                  state_factor=0.0, chr_level=False, max_batch=None,
-                 max_wait_ms=5.0, fused_select=False):
+                 max_wait_ms=5.0, fused_select=False,
+                 paged_rerank=False):
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = device
@@ -56,6 +59,7 @@ class SummarizerService:
         self.state_factor = float(state_factor)
         self.chr_level = bool(chr_level)
         self.fused_select = bool(fused_select)
+        self.paged_rerank = bool(paged_rerank)
         self.max_batch = int(max_batch or max(1, 64 // self.k))
         self.max_wait_s = float(max_wait_ms) / 1000.0
         self.model_path = str(model_path)
@@ -186,7 +190,8 @@ class SummarizerService:
                 maxlen=maxlens if maxlens else self.maxlen, use_unk=True,
                 kl_factor=self.kl_factor, ctx_factor=self.ctx_factor,
                 state_factor=self.state_factor,
-                fused_select=self.fused_select)
+                fused_select=self.fused_select,
+                paged_rerank=self.paged_rerank)
         results = []
         for src_words, (sample, score, alphas) in zip(srcs, outs):
             score = numpy.array(score, dtype=numpy.float64)

@@ -20,12 +20,15 @@ from nats_amd.decode.beam import gen_sample
 from nats_amd.models.distraction import NatsModel, default_options
 
 
-def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False):
+def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False,
+        paged=False):
     n_tokens = 0
     t0 = time.perf_counter()
     if batched:
         from nats_amd.decode.batched import gen_sample_batched
         extra = {"fused_select": True} if fused else {}
+        if paged:
+            extra["paged_rerank"] = True
         sb = max(1, 64 // k)
         for base in range(0, len(xs), sb):
             outs = gen_sample_batched(model, xs[base:base + sb], k=k,
@@ -84,10 +87,15 @@ def main():
     variants.append(("beam+batched" + suffix, graph, 0.0, True, True))
     variants.append(("beam+distraction+batched" + suffix, graph, 0.5, True,
                      True))
-    for name, graph, lam, batched, fused in variants:
-        run(model, xs[:2], args.k, args.maxlen, graph, lam, batched, fused)
+    variants = [v + (False,) for v in variants]
+    # paged rerank histories (ops.RerankHistory), appended last
+    variants.append(("beam+distraction+batched" + suffix + "+pagedrerank",
+                     graph, 0.5, True, True, True))
+    for name, graph, lam, batched, fused, paged in variants:
+        run(model, xs[:2], args.k, args.maxlen, graph, lam, batched, fused,
+            paged)
         sps, ntok = run(model, xs, args.k, args.maxlen, graph, lam, batched,
-                        fused)
+                        fused, paged)
         print(json.dumps({
             "metric": "summaries_per_sec", "variant": name, "value": sps,
             "beam": args.k, "n": args.n, "src_len": args.src,

@@ -33,6 +33,9 @@ def main():
     ap.add_argument("--max-wait-ms", type=float, default=5.0)
     ap.add_argument("--fused-select", action="store_true",
                     help="one fused candidate-selection op per decode step")
+    ap.add_argument("--paged-rerank", action="store_true",
+                    help="paged distraction-rerank histories: one penalty "
+                         "call per decode step for all sentences")
     args = ap.parse_args()
 
     import uvicorn
@@ -45,7 +48,7 @@ def main():
         kl_factor=args.kl_factor, ctx_factor=args.ctx_factor,
         state_factor=args.state_factor, chr_level=args.chr_level,
         max_batch=args.max_batch, max_wait_ms=args.max_wait_ms,
-        fused_select=args.fused_select)
+        fused_select=args.fused_select, paged_rerank=args.paged_rerank)
     app = create_app(service)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 

@@ -108,6 +108,35 @@ class NatsModel(nn.Module):
         the gather kernel (ops/hip/embed.hip)."""
         return ops.embed_gather(self.P["Wemb"], ids, shift=shift)
 
+    def _encode_scans(self, x, x_mask):
+        """The stacked bidirectional scans: (h_f, h_r) (T,B,H) of the last
+        layer, h_r in the reverse scan's own (flipped) time order; lower
+        layers feed the next one their concatenated context."""
+        P = self.P
+        emb = self.embed(x)
+        maskr = x_mask.flip(0) if x_mask is not None else None
+
+        def bi_layer(inp, pf, pr):
+            inpr = inp.flip(0)
+            xg = ops.linear_bias(inp, P[pf + "_W"], P[pf + "_b"])
+            xc = ops.linear_bias(inp, P[pf + "_Wx"], P[pf + "_bx"])
+            xgr = ops.linear_bias(inpr, P[pr + "_W"], P[pr + "_b"])
+            xcr = ops.linear_bias(inpr, P[pr + "_Wx"], P[pr + "_bx"])
+            return ops.gru_scan_bidir(
+                xg, xc, x_mask, P[pf + "_U"], P[pf + "_Ux"],
+                xgr, xcr, maskr, P[pr + "_U"], P[pr + "_Ux"])
+
+        proj, projr = bi_layer(emb, "encoder", "encoder_r")
+        for l in range(1, self.options.get("enc_depth", 1)):
+            ctx = torch.cat([proj, projr.flip(0)], dim=-1)
+            proj, projr = bi_layer(ctx, "encoder_l%d" % l,
+                                   "encoder_r_l%d" % l)
+        return proj, projr
+
+    def _init_state(self, ctx_mean):
+        return torch.tanh(ctx_mean @ self.P["ff_state_W"] +
+                          self.P["ff_state_b"])
+
     def encode(self, x, x_mask=None):
         """Bidirectional encode + decoder init state.
 
@@ -116,32 +145,9 @@ class NatsModel(nn.Module):
         (nats.py:810); with a mask it is the masked mean (nats.py:717).
         Returns (ctx (T,B,2H), init_state (B,H)).
         """
-        P = self.P
-        emb = self.embed(x)
-        maskr = x_mask.flip(0) if x_mask is not None else None
-
-        def bi_layer(inp, pf, pr):
-            inpr = inp.flip(0)
-            xg = inp @ P[pf + "_W"] + P[pf + "_b"]
-            xc = inp @ P[pf + "_Wx"] + P[pf + "_bx"]
-            xgr = inpr @ P[pr + "_W"] + P[pr + "_b"]
-            xcr = inpr @ P[pr + "_Wx"] + P[pr + "_bx"]
-            proj, projr = ops.gru_scan_bidir(
-                xg, xc, x_mask, P[pf + "_U"], P[pf + "_Ux"],
-                xgr, xcr, maskr, P[pr + "_U"], P[pr + "_Ux"])
-            return torch.cat([proj, projr.flip(0)], dim=-1)
-
-        ctx = bi_layer(emb, "encoder", "encoder_r")
-        for l in range(1, self.options.get("enc_depth", 1)):
-            ctx = bi_layer(ctx, "encoder_l%d" % l, "encoder_r_l%d" % l)
-        if x_mask is not None:
-            ctx_mean = ((ctx * x_mask.unsqueeze(-1)).sum(0) /
-                        x_mask.sum(0).unsqueeze(-1))
-        else:
-            ctx_mean = ctx.mean(0)
-        init_state = torch.tanh(ctx_mean @ self.P["ff_state_W"] +
-                                self.P["ff_state_b"])
-        return ctx, init_state
+        proj, projr = self._encode_scans(x, x_mask)
+        ctx = torch.cat([proj, projr.flip(0)], dim=-1)
+        return ctx, self._init_state(ops.eager.context_mean(ctx, x_mask))
 
     def project_ctx(self, ctx):
         """Attention keys, hoisted out of the decode loop (nats.py:493-494)."""
@@ -149,9 +155,15 @@ class NatsModel(nn.Module):
 
     def _dec_inputs(self, emb):
         P = self.P
-        yg = emb @ P["decoder_W"] + P["decoder_b"]
-        yc = emb @ P["decoder_Wx"] + P["decoder_bx"]
+        yg = ops.linear_bias(emb, P["decoder_W"], P["decoder_b"])
+        yc = ops.linear_bias(emb, P["decoder_Wx"], P["decoder_bx"])
         return yg, yc
+
+    def _readout_hidden(self, h, emb, ctxs):
+        P = self.P
+        return torch.tanh(h @ P["ff_logit_lstm_W"] + P["ff_logit_lstm_b"] +
+                          emb @ P["ff_logit_prev_W"] + P["ff_logit_prev_b"] +
+                          ctxs @ P["ff_logit_ctx_W"] + P["ff_logit_ctx_b"])
 
     def readout_logits(self, h, emb, ctxs):
         """tanh-fused readout + vocab projection (nats.py:753-761).
@@ -159,9 +171,7 @@ class NatsModel(nn.Module):
         All args (...,*) leading dims broadcastable; returns logits (...,V).
         """
         P = self.P
-        logit = torch.tanh(h @ P["ff_logit_lstm_W"] + P["ff_logit_lstm_b"] +
-                           emb @ P["ff_logit_prev_W"] + P["ff_logit_prev_b"] +
-                           ctxs @ P["ff_logit_ctx_W"] + P["ff_logit_ctx_b"])
+        logit = self._readout_hidden(h, emb, ctxs)
         return logit @ P["ff_logit_W"] + P["ff_logit_b"]
 
     def forward(self, x, x_mask, y, y_mask):
@@ -173,8 +183,11 @@ class NatsModel(nn.Module):
         the scans are latency-critical (one grid barrier per timestep)
         and any co-resident work inflates every barrier interval; the
         idle CUs are not free capacity. Reverted to sequential."""
-        ctx, init_state = self.encode(x, x_mask)
-        pctx = self.project_ctx(ctx)
+        P = self.P
+        proj, projr = self._encode_scans(x, x_mask)
+        ctx, ctx_mean, pctx = ops.encoder_head(
+            proj, projr, x_mask, P["decoder_Wc_att"], P["decoder_b_att"])
+        init_state = self._init_state(ctx_mean)
 
         emb_shifted = self.embed(y, shift=True)
         yg, yc = self._dec_inputs(emb_shifted)
@@ -182,7 +195,8 @@ class NatsModel(nn.Module):
         h2s, ctxs, alphas, _, _ = ops.cond_gru_scan(
             yg, yc, y_mask, init_state, ctx, x_mask, pctx, self.P)
 
-        logits = self.readout_logits(h2s, emb_shifted, ctxs)
+        logits = ops.linear_bias(self._readout_hidden(h2s, emb_shifted, ctxs),
+                                 P["ff_logit_W"], P["ff_logit_b"])
         T, B, V = logits.shape
         cost = ops.softmax_xent(logits.reshape(T * B, V), y.reshape(-1))
         cost = cost.reshape(T, B)

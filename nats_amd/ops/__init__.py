@@ -202,6 +202,44 @@ def cond_gru_step(h_prev, x_g, x_c, ctx, ctx_mask, pctx, acc_ctx, acc_alpha, P):
                                acc_ctx, acc_alpha, P)
 
 
+def _autocast_bf16():
+    return (torch.is_autocast_enabled("cuda")
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+
+def linear_bias(x, W, b):
+    """x (..., K) @ W (K, N) + b (N,): the hoisted input projections and
+    the training vocab projection.
+
+    Under bf16 autocast on GPU the result is bf16: the value
+    ``(x @ W + b).to(bfloat16)``, which is what the scan and softmax
+    kernels round the fp32 sum to anyway, from one bias+round pass over the
+    GEMM output; the backward column-sums the bf16 gradient in place.
+    Everywhere else this is the plain expression.
+    """
+    if _use_hip(x, W) and _autocast_bf16():
+        from .io_fusion import linear_bias_hip
+        return linear_bias_hip(x, W, b)
+    return eager.linear_bias(x, W, b)
+
+
+def encoder_head(h_f, h_r, x_mask, Wc_att, b_att):
+    """Context assembly after the last encoder layer, for training:
+    (ctx (T,B,2H) = [h_f | flip(h_r)], ctx_mean (B,2H), pctx (T,B,A)).
+    ``h_r`` is in the reverse scan's own time order.
+
+    Under bf16 autocast on GPU ctx is returned in bf16 (the only form the
+    decoder scan and the key projection read) from one pass over the scan
+    outputs, and the backward sums the three gradient terms of ctx
+    straight into the tensors the scan backward consumes. ctx_mean is
+    torch's own fp32 reduction, bit for bit the value of the expression.
+    """
+    if _use_hip(h_f, Wc_att) and _autocast_bf16():
+        from .io_fusion import encoder_head_hip
+        return encoder_head_hip(h_f, h_r, x_mask, Wc_att, b_att)
+    return eager.encoder_head(h_f, h_r, x_mask, Wc_att, b_att)
+
+
 def embed_gather(Wemb, ids, shift=False):
     """Embedding gather, optionally fused with the decoder's
     shift-right-by-one (BOS row = zeros). Semantics: nats.py:700-701

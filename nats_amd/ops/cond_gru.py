@@ -170,10 +170,10 @@ class CondGRUScanFn(torch.autograd.Function):
         dU, dUx = gru_weight_grads(h2_all, dpre2_all, init_state)
 
         # encoder-context grad from the attention weighted sum, factored
-        # over time: dctx[s,b,c] = sum_t alpha[t,b,s] * dctx_pre[t,b,c]
+        # over time: dctx[s,b,c] = sum_t alpha[t,b,s] * dctx_pre[t,b,c];
+        # a bf16 ctx (ops.encoder_head) takes the bf16 bmm result as it is
         dctx_enc = torch.einsum(
-            "tbs,tbc->sbc", alphas_all.to(torch.bfloat16),
-            dctxpre_all).float()
+            "tbs,tbc->sbc", alphas_all.to(torch.bfloat16), dctxpre_all)
 
         ygd, ctxd, pctxd, initd = fctx.in_dtypes
         return (dyg.to(ygd), dyc.to(ygd), None, dh_carry.to(initd),

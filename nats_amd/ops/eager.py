@@ -152,6 +152,29 @@ def softmax_xent(logits, targets):
     return -logp.gather(1, targets.unsqueeze(1)).squeeze(1)
 
 
+def linear_bias(x, W, b):
+    """Hoisted input / vocab projection x @ W + b."""
+    return x @ W + b
+
+
+def context_mean(ctx, x_mask):
+    """Masked time-mean of the context (nats.py:717); the plain mean
+    without a mask (the sampler, nats.py:810)."""
+    if x_mask is not None:
+        return ((ctx * x_mask.unsqueeze(-1)).sum(0) /
+                x_mask.sum(0).unsqueeze(-1))
+    return ctx.mean(0)
+
+
+def encoder_head(h_f, h_r, x_mask, Wc_att, b_att):
+    """Context assembly from the two scan outputs (h_r in the reverse
+    scan's own time order): ctx = [h_f | flip(h_r)] (nats.py:713), its
+    masked mean and the attention keys ctx @ Wc_att + b_att
+    (nats.py:493-494). Returns (ctx, ctx_mean, pctx)."""
+    ctx = torch.cat([h_f, h_r.flip(0)], dim=-1)
+    return ctx, context_mean(ctx, x_mask), ctx @ Wc_att + b_att
+
+
 NEG_UNK = math.log(1e-20)  # log-probability UNK is pinned to (nats.py:1001)
 
 

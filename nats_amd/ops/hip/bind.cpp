@@ -86,6 +86,15 @@ torch::Tensor pack_gru1_weights_hip(torch::Tensor U_1, torch::Tensor W_1,
                                     long Hpad, long Cpad);
 torch::Tensor embed_scatter_add(torch::Tensor dout, torch::Tensor ids,
                                 long V, long shift_rows);
+torch::Tensor bias_cast_(torch::Tensor g, torch::Tensor b);
+torch::Tensor colsum_bf16(torch::Tensor g);
+long colsum_rows_per_block();
+torch::Tensor ctx_head_fwd(torch::Tensor hf, torch::Tensor hr);
+std::vector<torch::Tensor> ctx_head_bwd(torch::Tensor denc,
+                                        torch::Tensor dproj,
+                                        torch::Tensor dmean,
+                                        c10::optional<torch::Tensor> mask,
+                                        torch::Tensor cnt);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pack_fwd_weights", &pack_fwd_weights_hip,
@@ -98,6 +107,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "embedding gather (+fused decoder shift)");
   m.def("embed_scatter_add", &embed_scatter_add,
         "embedding backward scatter-add");
+  m.def("bias_cast_", &bias_cast_,
+        "in-place y = bf16(float(g) + b) on a bf16 GEMM result");
+  m.def("colsum_bf16", &colsum_bf16,
+        "fp32 column sums of a row-strided bf16 matrix (fixed order)");
+  m.def("colsum_rows_per_block", &colsum_rows_per_block,
+        "rows one colsum_bf16 partial block reduces");
+  m.def("ctx_head_fwd", &ctx_head_fwd,
+        "bf16 [h_f | flip(h_r)] context");
+  m.def("ctx_head_bwd", &ctx_head_bwd,
+        "context gradient terms summed into the scans' dh tensors");
   m.def("gru_scan_fwd", &gru_scan_fwd, "fused GRU scan forward");
   m.def("gru_scan_bwd", &gru_scan_bwd, "fused GRU scan backward");
   m.def("gru_scan_fwd_bidir", &gru_scan_fwd_bidir,

@@ -1,5 +1,6 @@
 """Shared input builders, oracle runs and comparison helpers of the kernel
-tests (tests/test_gpu_kernels.py, tests/test_gpu_kernel_edges.py).
+tests (tests/test_gpu_kernels.py, tests/test_gpu_kernel_edges.py,
+tests/test_gru_kloop_edges.py).
 
 The oracle is always nats_amd.ops.eager. It is run in three ways:
   * fp64: the reference every comparison is made against,
@@ -177,7 +178,25 @@ def alphas_rel_err(alphas, ref_alphas, ctx_mask):
     return float(rel[sel.expand_as(rel)].max())
 
 
+def _gru_kloop_inputs(T, B, H, seed):
+    """GRU scan inputs for hidden sizes up to the production ones. U and Ux
+    are N(0,1) * 2 * H^-0.5: H^-0.5 keeps the gates out of saturation at
+    H = 1000, the factor 2 keeps the recurrent term large enough that one
+    missing 32-wide K slice of it is visible. Lengths lie in [2, T].
+    Returns ((xg, xc, U, Ux, mask), h0)."""
+    g = torch.Generator().manual_seed(seed)
+    xg = torch.randn(T, B, 2 * H, generator=g)
+    xc = torch.randn(T, B, H, generator=g)
+    U = 2 * H ** -0.5 * torch.randn(H, 2 * H, generator=g)
+    Ux = 2 * H ** -0.5 * torch.randn(H, H, generator=g)
+    lens = torch.randint(2, T + 1, (B,), generator=g)
+    mask = (torch.arange(T).unsqueeze(1) < lens.unsqueeze(0)).float()
+    h0 = 0.5 * torch.randn(B, H, generator=g)
+    return (xg, xc, U, Ux, mask), h0
+
+
 GRU_GRAD_NAMES = ("xg", "xc", "U", "Ux", "h0")
+GRU_BIDIR_GRAD_NAMES = ("xg0", "xc0", "U0", "Ux0", "xg1", "xc1", "U1", "Ux1")
 
 
 def run_gru_scan(fn, inputs, h0, dev="cpu", dtype=torch.float32,
@@ -196,3 +215,26 @@ def run_gru_scan(fn, inputs, h0, dev="cpu", dtype=torch.float32,
     return (h.detach().cpu().to(dtype),
             {n: t.grad.detach().cpu().to(dtype)
              for n, t in zip(GRU_GRAD_NAMES, leaves)})
+
+
+def run_gru_scan_bidir(fn, inputs0, inputs1, dev="cpu", dtype=torch.float32,
+                       bf16_operands=False):
+    """Bidirectional counterpart of run_gru_scan: ``fn(xg0, xc0, mask0, U0,
+    Ux0, xg1, xc1, mask1, U1, Ux1)`` -> (h_fwd, h_bwd), both from a zero
+    state, with the loss of weighted_loss over the two outputs. inputs0 and
+    inputs1 are (xg, xc, U, Ux, mask) per direction; a mask may be None.
+    Returns ((h_fwd, h_bwd), grads) as detached CPU tensors of ``dtype``;
+    grads maps GRU_BIDIR_GRAD_NAMES."""
+    leaves, args = [], []
+    for xg, xc, U, Ux, mask in (inputs0, inputs1):
+        lv = [t.clone().to(device=dev, dtype=dtype).requires_grad_(True)
+              for t in (xg, xc, U, Ux)]
+        a = [round_bf16(t) for t in lv] if bf16_operands else lv
+        m = None if mask is None else mask.to(device=dev, dtype=dtype)
+        leaves += lv
+        args += [a[0], a[1], m, a[2], a[3]]
+    hs = fn(*args)
+    weighted_loss(hs, dev, dtype).backward()
+    return (tuple(h.detach().cpu().to(dtype) for h in hs),
+            {n: t.grad.detach().cpu().to(dtype)
+             for n, t in zip(GRU_BIDIR_GRAD_NAMES, leaves)})

@@ -20,6 +20,10 @@ per-sentence top-k loop becomes one ops.beam_select call per step
 the rerank histories of all sentences live in one ops.RerankHistory: each
 step's rows are stored once and an int32 ancestor table is reshuffled
 instead of the histories themselves (docs/DESIGN.md, "Rerank histories").
+With ``shared_ctx=True`` the per-sentence context is never expanded to one
+column per hypothesis row: it is rounded to bf16 once per micro-batch and
+the attention kernel reads it through the row -> sentence table
+(ops.cond_gru_step_shared; profiles/README.md, "Decode v6").
 
 Numerics note: results are mathematically identical to per-sentence
 gen_sample, but not bitwise — the batched masked-mean init state and
@@ -107,7 +111,7 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
 def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                        kl_factor=0.0, ctx_factor=0.0, state_factor=0.0,
                        use_graph=True, fused_select=False,
-                       paged_rerank=False):
+                       paged_rerank=False, shared_ctx=False):
     """Beam-decode a list of sources jointly.
 
     fused_select: pick every sentence's candidates with one
@@ -120,6 +124,11 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
     table) and compute every row's penalties in one call per step, instead
     of re-gathering dense per-sentence histories. Same penalties bit for
     bit; a no-op when all three factors are 0. Opt-in.
+
+    shared_ctx: attend every hypothesis row to its sentence's column of
+    the per-sentence context (bf16, rounded once) through the sent_idx
+    table, instead of gathering ctx / pctx / mask to one column per row
+    and re-rounding them on every step. Same results bit for bit. Opt-in.
 
     xs: list of (T_i, 1) int64 tensors (same device as model).
     maxlen: an int, or a per-sentence list (serving: each request brings
@@ -179,15 +188,23 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
     for i in range(S):
         ctx_pad[:lens[i], i] = ctx_all[:lens[i], i]
     ctx_mask_s = src_mask
-    pctx_pad = model.project_ctx(ctx_pad)
+    graphed = use_graph and device.type == "cuda"
+    if shared_ctx and not graphed:
+        # bf16 once per micro-batch; pctx from the fp32 context as ever
+        ctx_dec, cmask_dec, pctx_pad = model.decode_context(ctx_pad,
+                                                            ctx_mask_s)
+    else:
+        pctx_pad = model.project_ctx(ctx_pad)
 
     # hipGraph-captured f_next for the shared step (fixed row budget S*k;
-    # the per-step sentence gather runs inside the graph)
+    # the per-step sentence gather, or with shared_ctx the row -> sentence
+    # table read, runs inside the graph)
     stepper = None
-    if use_graph and device.type == "cuda":
+    if graphed:
         from .graph import get_batched_stepper
         stepper = get_batched_stepper(model, ctx_pad.float(), ctx_mask_s,
-                                      pctx_pad.float(), S * k)
+                                      pctx_pad.float(), S * k,
+                                      shared_ctx=shared_ctx)
 
     NEG_UNK = math.log(1e-20)
 
@@ -213,13 +230,13 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 sent_rows + sum((st[i]["prows"] for i in alive), []),
                 device=device)
             sent_idx, parent_dev = up[:len(sent_rows)], up[len(sent_rows):]
-        else:
+        elif stepper is not None or not shared_ctx:
             sent_idx = torch.tensor(sent_rows, device=device)
         y = torch.cat([dstate[i]["w"] for i in alive])
         state = torch.cat([dstate[i]["state"] for i in alive])
         acc_c = torch.cat([dstate[i]["acc_c"] for i in alive])
         acc_a = torch.cat([dstate[i]["acc_a"] for i in alive])
-        if stepper is None:
+        if stepper is None and not shared_ctx:
             ctx_b = ctx_pad[:, sent_idx]
             cmask_b = ctx_mask_s[:, sent_idx]
             pctx_b = pctx_pad[:, sent_idx]
@@ -230,6 +247,10 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                                 acc_a.float())
             probs, h2, alpha, ctx_t, acc_c, acc_a = [
                 o[:rows] for o in outs]
+        elif shared_ctx:
+            probs, _, h2, alpha, ctx_t, acc_c, acc_a = model.f_next(
+                y, ctx_dec, cmask_dec, pctx_pad, state, acc_c, acc_a,
+                sample_draw=False, row_src=sent_rows)  # validated, 1 upload
         else:
             probs, _, h2, alpha, ctx_t, acc_c, acc_a = model.f_next(
                 y, ctx_b, cmask_b, pctx_b, state, acc_c, acc_a,

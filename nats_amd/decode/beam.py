@@ -92,10 +92,14 @@ def distraction_penalties_gpu(hist_a, hist_c, hist_s, cur_a, cur_c, cur_s,
 @torch.no_grad()
 def gen_sample(model, x, k=1, maxlen=30, stochastic=True, argmax=False,
                use_unk=False, kl_factor=0.0, ctx_factor=0.0, state_factor=0.0,
-               generator=None, use_graph=False):
+               generator=None, use_graph=False, shared_ctx=False):
     """Generate one summary by beam search or stochastic sampling.
 
     model: NatsModel; x: (T,1) int64 tensor on the model's device.
+    shared_ctx: every hypothesis row reads the sentence's one (Ts,1,C)
+    context column (bf16, rounded once) through a row -> source table of
+    zeros, instead of a context expanded to k columns and re-rounded on
+    every step. Same results bit for bit. Opt-in.
     Returns (sample, sample_score, sample_dec_alphas) exactly like the
     reference: beam mode gives lists (one per finished hypothesis);
     stochastic mode gives a flat token list and a scalar score.
@@ -118,7 +122,13 @@ def gen_sample(model, x, k=1, maxlen=30, stochastic=True, argmax=False,
     hyp_states_dis = [[]] * live_k
 
     init_state, ctx0 = model.f_init(x)
-    pctx0 = model.project_ctx(ctx0)
+    graphed = use_graph and not stochastic and device.type == "cuda"
+    if shared_ctx and not graphed:
+        ctx_dec, _, pctx0 = model.decode_context(ctx0)
+        zeros_src = torch.zeros(k, dtype=torch.int32 if ctx0.is_cuda
+                                else torch.int64, device=device)
+    else:
+        pctx0 = model.project_ctx(ctx0)
     next_state = init_state                               # (1,H)
     next_w = torch.full((1,), -1, dtype=torch.int64, device=device)
     C = ctx0.shape[2]
@@ -129,9 +139,10 @@ def gen_sample(model, x, k=1, maxlen=30, stochastic=True, argmax=False,
     # hipGraph-captured decode step (beam mode on GPU): the whole f_next
     # kernel chain replays as one graph per step
     stepper = None
-    if use_graph and not stochastic and device.type == "cuda":
+    if graphed:
         from .graph import get_stepper
-        stepper = get_stepper(model, ctx0.float(), pctx0.float(), k)
+        stepper = get_stepper(model, ctx0.float(), pctx0.float(), k,
+                              shared_ctx=shared_ctx)
 
     any_lambda = (kl_factor > 0.0 or ctx_factor > 0.0 or state_factor > 0.0)
     # device-resident rerank histories (GPU path); the numpy histories are
@@ -151,6 +162,12 @@ def gen_sample(model, x, k=1, maxlen=30, stochastic=True, argmax=False,
             ctxs = ctxs_k[:live_k]
             acc_ctx = accC_k[:live_k]
             acc_alpha = accA_k[:live_k]
+        elif shared_ctx:
+            probs, w_sample, next_state, dec_alphas, ctxs, acc_ctx, \
+                acc_alpha = model.f_next(
+                    next_w, ctx_dec, None, pctx0, next_state, acc_ctx,
+                    acc_alpha, generator=generator, sample_draw=stochastic,
+                    row_src=zeros_src[:live_k])
         else:
             ctx = ctx0.expand(Ts, live_k, C)
             pctx = pctx0.expand(Ts, live_k, pctx0.shape[2])

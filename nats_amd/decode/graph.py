@@ -11,6 +11,11 @@ length Ts); the beam keeps that many rows alive (dead/padded rows carry
 copies of row 0, harmless — callers slice [:live]). Host-side feedback
 between replays (parent gather after rank selection) writes the static
 input buffers with index copies.
+
+Both steppers have a ``shared_ctx`` mode: the context is kept once per
+source, rounded to bf16 when it is set, and the captured f_next reads it
+through a static int32 row -> source table (ops.cond_gru_step_shared), so
+no per-row copy of ctx / pctx / mask exists inside or outside the graph.
 """
 
 import weakref
@@ -23,7 +28,7 @@ _STEPPER_CACHE = weakref.WeakKeyDictionary()
 _MAX_PER_FAMILY = 8
 
 
-def _cached_stepper(cls, model, shape, context, rows):
+def _cached_stepper(cls, model, shape, context, rows, **mode):
     """One stepper of class ``cls`` per (model, shape): the captured graph
     is reused across inputs of the same shape — a hit only refreshes the
     static context buffers. Packed weights are baked into the graph at
@@ -41,25 +46,28 @@ def _cached_stepper(cls, model, shape, context, rows):
         family = [kk for kk in per_model if kk[0] is cls]
         if len(family) >= _MAX_PER_FAMILY:
             per_model.pop(family[0])
-        st = per_model[key] = cls(model, *context, rows)
+        st = per_model[key] = cls(model, *context, rows, **mode)
     else:
         st.set_context(*context)
     return st
 
 
-def get_stepper(model, ctx0, pctx0, k):
-    """Cached GraphDecodeStepper per (model, Ts, k)."""
+def get_stepper(model, ctx0, pctx0, k, shared_ctx=False):
+    """Cached GraphDecodeStepper per (model, Ts, k, shared_ctx)."""
     return _cached_stepper(GraphDecodeStepper, model,
-                           (int(ctx0.shape[0]), int(k)), (ctx0, pctx0), k)
+                           (int(ctx0.shape[0]), int(k), bool(shared_ctx)),
+                           (ctx0, pctx0), k, shared_ctx=bool(shared_ctx))
 
 
-def get_batched_stepper(model, ctx_pad, ctx_mask, pctx_pad, R):
-    """Cached BatchedGraphStepper per (model, Ts, S, R) — reused across
-    same-shaped micro-batches (serving)."""
+def get_batched_stepper(model, ctx_pad, ctx_mask, pctx_pad, R,
+                        shared_ctx=False):
+    """Cached BatchedGraphStepper per (model, Ts, S, R, shared_ctx) —
+    reused across same-shaped micro-batches (serving)."""
     return _cached_stepper(
         BatchedGraphStepper, model,
-        (int(ctx_pad.shape[0]), int(ctx_pad.shape[1]), int(R)),
-        (ctx_pad, ctx_mask, pctx_pad), R)
+        (int(ctx_pad.shape[0]), int(ctx_pad.shape[1]), int(R),
+         bool(shared_ctx)),
+        (ctx_pad, ctx_mask, pctx_pad), R, shared_ctx=bool(shared_ctx))
 
 
 class _GraphStepper:
@@ -117,14 +125,23 @@ class _GraphStepper:
 
 class GraphDecodeStepper(_GraphStepper):
     """Single-sentence beam: step(y, state, acc_ctx, acc_alpha) against the
-    sentence's context expanded to all k rows, no mask."""
+    sentence's context expanded to all k rows, no mask. ``shared_ctx``: the
+    context stays (Ts,1,C) in bf16 and all k rows read its one column."""
 
-    def __init__(self, model, ctx0, pctx0, k):
+    def __init__(self, model, ctx0, pctx0, k, shared_ctx=False):
         """ctx0 (Ts,1,C), pctx0 (Ts,1,A) from f_init/project_ctx."""
         Ts, _, C = ctx0.shape
         super().__init__(model, k, Ts, C, ctx0.device)
-        self.ctx = ctx0.expand(Ts, k, C).contiguous()
-        self.pctx = pctx0.expand(Ts, k, pctx0.shape[2]).contiguous()
+        self.shared_ctx = shared_ctx
+        if shared_ctx:
+            self.ctx = ctx0.to(torch.bfloat16).contiguous().clone()
+            self.pctx = pctx0.float().contiguous().clone()
+            self.row_src = torch.zeros(k, dtype=torch.int32,
+                                       device=ctx0.device)
+        else:
+            self.ctx = ctx0.expand(Ts, k, C).contiguous()
+            self.pctx = pctx0.expand(Ts, k, pctx0.shape[2]).contiguous()
+            self.row_src = None
 
     def set_context(self, ctx0, pctx0):
         """Refresh the static context buffers for a new source sequence
@@ -135,7 +152,7 @@ class GraphDecodeStepper(_GraphStepper):
     def _run(self):
         return self.model.f_next(self.y_in, self.ctx, None, self.pctx,
                                  self.state_in, self.accC_in, self.accA_in,
-                                 sample_draw=False)
+                                 sample_draw=False, row_src=self.row_src)
 
 
 class BatchedGraphStepper(_GraphStepper):
@@ -144,19 +161,38 @@ class BatchedGraphStepper(_GraphStepper):
     static row budget R (= S*k). The per-step context gather
     ctx_pad[:, sent_idx] happens INSIDE the graph from a static sent_idx
     buffer, so hypothesis->sentence routing changes never force
-    recapture."""
+    recapture. ``shared_ctx``: no gather at all — ctx_pad is held in bf16
+    and ``step`` writes its sent_idx argument into ``row_src``, the static
+    int32 row -> source table the attention kernel reads the per-sentence
+    context through (``sent_idx``, the gather's int64 buffer, is then
+    None)."""
 
-    def __init__(self, model, ctx_pad, ctx_mask, pctx_pad, R):
+    def __init__(self, model, ctx_pad, ctx_mask, pctx_pad, R,
+                 shared_ctx=False):
         Ts, S, C = ctx_pad.shape
         super().__init__(model, R, Ts, C, ctx_pad.device)
+        self.shared_ctx = shared_ctx
         # own the static buffers (a caller's tensor may alias freed memory
         # by the next micro-batch)
-        self.ctx_pad = ctx_pad.contiguous().clone()
+        if shared_ctx:
+            self.ctx_pad = ctx_pad.to(torch.bfloat16).contiguous().clone()
+        else:
+            self.ctx_pad = ctx_pad.contiguous().clone()
         self.ctx_mask = ctx_mask.float().contiguous().clone()
-        self.pctx_pad = pctx_pad.contiguous().clone()
-        self.sent_idx = torch.zeros(R, dtype=torch.int64,
-                                    device=ctx_pad.device)
-        self.inputs = (self.sent_idx,) + self.inputs
+        self.pctx_pad = pctx_pad.float().contiguous().clone() if shared_ctx \
+            else pctx_pad.contiguous().clone()
+        # step() writes the caller's sent_idx into this buffer; in shared
+        # mode it is the kernel's int32 row -> source table (the write
+        # converts)
+        self.sent_idx = self.row_src = None
+        if shared_ctx:
+            self.row_src = torch.zeros(R, dtype=torch.int32,
+                                       device=ctx_pad.device)
+            self.inputs = (self.row_src,) + self.inputs
+        else:
+            self.sent_idx = torch.zeros(R, dtype=torch.int64,
+                                        device=ctx_pad.device)
+            self.inputs = (self.sent_idx,) + self.inputs
 
     def set_context(self, ctx_pad, ctx_mask, pctx_pad):
         self.ctx_pad.copy_(ctx_pad)
@@ -164,6 +200,12 @@ class BatchedGraphStepper(_GraphStepper):
         self.pctx_pad.copy_(pctx_pad)
 
     def _run(self):
+        if self.shared_ctx:
+            return self.model.f_next(self.y_in, self.ctx_pad, self.ctx_mask,
+                                     self.pctx_pad, self.state_in,
+                                     self.accC_in, self.accA_in,
+                                     sample_draw=False,
+                                     row_src=self.row_src)
         ctx_b = self.ctx_pad.index_select(1, self.sent_idx)
         cmask_b = self.ctx_mask.index_select(1, self.sent_idx)
         pctx_b = self.pctx_pad.index_select(1, self.sent_idx)

@@ -153,6 +153,20 @@ class NatsModel(nn.Module):
         """Attention keys, hoisted out of the decode loop (nats.py:493-494)."""
         return ctx @ self.P["decoder_Wc_att"] + self.P["decoder_b_att"]
 
+    def decode_context(self, ctx, ctx_mask=None):
+        """The per-source context operands of shared-context decode
+        (f_next with ``row_src``): (ctx_dec, mask, pctx). pctx is projected
+        from the fp32 context as everywhere else; ctx_dec is the bf16 copy
+        the attention kernel reads, rounded here once instead of once per
+        step. Where the step runs eager (on CPU, or with the kernels
+        switched off by the environment) it is the context itself: the
+        eager step does not round its operands."""
+        pctx = self.project_ctx(ctx)
+        ctx_dec = (ctx.to(torch.bfloat16).contiguous() if ops._use_hip(ctx)
+                   else ctx)
+        mask = None if ctx_mask is None else ctx_mask.float().contiguous()
+        return ctx_dec, mask, pctx
+
     def _dec_inputs(self, emb):
         P = self.P
         yg = ops.linear_bias(emb, P["decoder_W"], P["decoder_b"])
@@ -217,18 +231,27 @@ class NatsModel(nn.Module):
 
     @torch.no_grad()
     def f_next(self, y_prev, ctx, ctx_mask, pctx, state, acc_ctx, acc_alpha,
-               generator=None, sample_draw=True):
+               generator=None, sample_draw=True, row_src=None):
         """One decode step (f_next, nats.py:821-871).
 
         y_prev (B,) int64, -1 marks BOS (embedding = zeros, nats.py:827-829).
+        ``row_src`` (B,): ctx / ctx_mask / pctx hold one column per source
+        (decode_context) and row b attends to column row_src[b], instead of
+        one column per row.
         Returns (probs (B,V), sample (B,), state (B,H), alpha (B,Ts),
         ctx_t (B,C), acc_ctx, acc_alpha).
         """
         emb = self.embed(y_prev.clamp_min(0))
         emb = torch.where((y_prev < 0).unsqueeze(1), torch.zeros_like(emb), emb)
         yg, yc = self._dec_inputs(emb)
-        h2, ctx_t, alpha_t, acc_ctx, acc_alpha = ops.cond_gru_step(
-            state, yg, yc, ctx, ctx_mask, pctx, acc_ctx, acc_alpha, self.P)
+        if row_src is not None:
+            h2, ctx_t, alpha_t, acc_ctx, acc_alpha = ops.cond_gru_step_shared(
+                state, yg, yc, ctx, ctx_mask, pctx, row_src, acc_ctx,
+                acc_alpha, self.P)
+        else:
+            h2, ctx_t, alpha_t, acc_ctx, acc_alpha = ops.cond_gru_step(
+                state, yg, yc, ctx, ctx_mask, pctx, acc_ctx, acc_alpha,
+                self.P)
         logits = self.readout_logits(h2, emb, ctx_t)
         probs = torch.softmax(logits.float(), dim=-1)
         if not sample_draw:

@@ -202,6 +202,92 @@ def cond_gru_step(h_prev, x_g, x_c, ctx, ctx_mask, pctx, acc_ctx, acc_alpha, P):
                                acc_ctx, acc_alpha, P)
 
 
+def _row_src_table(row_src, R, S, device):
+    """The row -> source-column table of cond_gru_step_shared as an int64
+    tensor for index_select (CPU / eager) or an int32 device tensor for the
+    kernel. A list or a CPU tensor is validated here (length R, entries in
+    [0, S)) and uploaded in one copy; a device tensor is taken on trust:
+    reading it would sync."""
+    if torch.is_tensor(row_src):
+        if row_src.dtype not in (torch.int32, torch.int64) or \
+                row_src.dim() != 1:
+            raise TypeError("cond_gru_step_shared: row_src must be a 1-d "
+                            "integer tensor, got %s %s"
+                            % (row_src.dtype, tuple(row_src.shape)))
+        if row_src.is_cuda:
+            if row_src.dtype != torch.int32:
+                raise TypeError("cond_gru_step_shared: a device row_src must "
+                                "be int32, got %s" % row_src.dtype)
+            if row_src.shape[0] != R:
+                raise ValueError("cond_gru_step_shared: row_src has %d "
+                                 "entries for %d rows"
+                                 % (row_src.shape[0], R))
+            return row_src
+        vals = row_src.tolist()
+    else:
+        vals = list(row_src)
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in vals):
+            raise TypeError("cond_gru_step_shared: row_src entries must be "
+                            "integers")
+    if len(vals) != R:
+        raise ValueError("cond_gru_step_shared: row_src has %d entries for "
+                         "%d rows" % (len(vals), R))
+    for v in vals:
+        if not 0 <= v < S:
+            raise ValueError("cond_gru_step_shared: row_src entry %d outside "
+                             "[0, S=%d)" % (v, S))
+    if device.type == "cuda":
+        return torch.tensor(vals, dtype=torch.int32).to(device,
+                                                        non_blocking=True)
+    return torch.tensor(vals, dtype=torch.int64, device=device)
+
+
+def cond_gru_step_shared(h_prev, x_g, x_c, ctx_src, ctx_mask_src, pctx_src,
+                         row_src, acc_ctx, acc_alpha, P):
+    """One decoder step against a context kept once per source: row r
+    attends to column ``row_src[r]`` of ctx_src (Ts,S,C), ctx_mask_src
+    (Ts,S) or None, pctx_src (Ts,S,A). Same returns and semantics as
+    ``cond_gru_step`` on ``ctx_src[:, row_src]``, ``ctx_mask_src[:,
+    row_src]``, ``pctx_src[:, row_src]``, without making those copies on
+    the GPU, and bit for bit its results there.
+
+    ``row_src``: a list or CPU int tensor (validated, one upload) or an
+    int32 device tensor (taken on trust). ``ctx_src`` is best passed in
+    bf16 (NatsModel.decode_context): the kernel then reads it in place;
+    any other dtype is cast on every call.
+    """
+    R = h_prev.shape[0]
+    if ctx_src.dim() != 3 or pctx_src.dim() != 3 or \
+            pctx_src.shape[:2] != ctx_src.shape[:2]:
+        raise ValueError("cond_gru_step_shared: ctx_src (Ts,S,C) and "
+                         "pctx_src (Ts,S,A) disagree: %s %s"
+                         % (tuple(ctx_src.shape), tuple(pctx_src.shape)))
+    S = ctx_src.shape[1]
+    if ctx_mask_src is not None and \
+            tuple(ctx_mask_src.shape) != tuple(ctx_src.shape[:2]):
+        raise ValueError("cond_gru_step_shared: ctx_mask_src must be (Ts,S)")
+    tab = _row_src_table(row_src, R, S, h_prev.device)
+    if _use_hip(h_prev, ctx_src):
+        from .cond_gru import cond_gru_step_hip
+        tab = tab.to(device=h_prev.device, dtype=torch.int32).contiguous()
+        if R <= MAX_KERNEL_BATCH:
+            return cond_gru_step_hip(h_prev, x_g, x_c, ctx_src, ctx_mask_src,
+                                     pctx_src, acc_ctx, acc_alpha, P, tab)
+        ctx_bf = ctx_src.to(torch.bfloat16).contiguous()  # once, not per chunk
+        return _run_chunks(lambda a, b: cond_gru_step_hip(
+            h_prev[a:b], x_g[a:b], x_c[a:b], ctx_bf, ctx_mask_src, pctx_src,
+            acc_ctx[a:b], acc_alpha[a:b], P, tab[a:b]), R, (0,) * 5,
+            concurrent=True)
+    idx = tab.to(device=ctx_src.device, dtype=torch.int64)
+    if ctx_src.dtype != pctx_src.dtype:
+        # a context already rounded for the kernel (a shared-mode graph
+        # stepper with the kernels switched off): eager runs in one dtype
+        ctx_src = ctx_src.to(pctx_src.dtype)
+    return eager.cond_gru_step_shared(h_prev, x_g, x_c, ctx_src,
+                                      ctx_mask_src, pctx_src, idx, acc_ctx,
+                                      acc_alpha, P)
+
+
 def _autocast_bf16():
     return (torch.is_autocast_enabled("cuda")
             and torch.get_autocast_dtype("cuda") == torch.bfloat16)

@@ -216,16 +216,21 @@ def _step_packed(P):
 
 @torch.no_grad()
 def cond_gru_step_hip(h_prev, x_g, x_c, ctx, ctx_mask, pctx, acc_ctx,
-                      acc_alpha, P):
-    """One decode step = T=1 fused scan with carried accumulators."""
+                      acc_alpha, P, row_src=None):
+    """One decode step = T=1 fused scan with carried accumulators.
+    ``row_src`` (R,) int32 on the device: row r reads column row_src[r] of
+    an S-column ctx / ctx_mask / pctx (ops.cond_gru_step_shared); a ctx
+    that is already bf16 and contiguous is passed through as it is."""
     ext = _hip_ext()
     packed = _step_packed(P)
+    shared = {} if row_src is None else {"row_src": row_src}
     outs = ext.cond_gru_fwd(
         x_g.unsqueeze(0).to(torch.bfloat16).contiguous(),
         x_c.unsqueeze(0).to(torch.bfloat16).contiguous(),
         None, h_prev, ctx.to(torch.bfloat16).contiguous(),
         ctx_mask.float().contiguous() if ctx_mask is not None else None,
         pctx.float().contiguous(), *packed,
-        acc_ctx.float().contiguous(), acc_alpha.float().contiguous())
+        acc_ctx.float().contiguous(), acc_alpha.float().contiguous(),
+        **shared)
     h2_all, ctxs_all, alphas_all, accC, accA = outs[:5]
     return h2_all[0], ctxs_all[0], alphas_all[0], accC, accA

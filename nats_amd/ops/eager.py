@@ -115,6 +115,18 @@ def cond_gru_step(h_prev, x_g, x_c, ctx, ctx_mask, pctx, acc_ctx, acc_alpha,
     return h2, ctx_t, alpha.t(), new_acc_ctx, new_acc_alpha
 
 
+def cond_gru_step_shared(h_prev, x_g, x_c, ctx_src, ctx_mask_src, pctx_src,
+                         row_src, acc_ctx, acc_alpha, P):
+    """cond_gru_step for rows that read column ``row_src[r]`` (int64
+    tensor) of a context kept once per source: gather, then the plain
+    step. The definition the shared-context kernel path is held to."""
+    return cond_gru_step(
+        h_prev, x_g, x_c, ctx_src.index_select(1, row_src),
+        (None if ctx_mask_src is None
+         else ctx_mask_src.index_select(1, row_src)),
+        pctx_src.index_select(1, row_src), acc_ctx, acc_alpha, P)
+
+
 def cond_gru_scan(y_gates, y_cand, mask, init_state, ctx, ctx_mask, pctx, P):
     """Decoder scan over target time (nats.py:596-608).
 

@@ -61,7 +61,8 @@ std::vector<torch::Tensor> cond_gru_fwd(
     torch::Tensor b1, torch::Tensor bx1, torch::Tensor Uatt,
     torch::Tensor catt, torch::Tensor Dwei, torch::Tensor Wcon,
     torch::Tensor Ucon,
-    c10::optional<torch::Tensor> accC0, c10::optional<torch::Tensor> accA0);
+    c10::optional<torch::Tensor> accC0, c10::optional<torch::Tensor> accA0,
+    c10::optional<torch::Tensor> row_src);
 std::vector<torch::Tensor> cond_gru_bwd(
     torch::Tensor dh2_all, c10::optional<torch::Tensor> dctxs_all,
     c10::optional<torch::Tensor> dalphas_all,
@@ -142,6 +143,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "segmented beam candidate selection (tile pass + merge pass)");
   m.def("fused_adadelta_step", &fused_adadelta_step,
         "fused multi-tensor global-norm clip + adadelta");
-  m.def("cond_gru_fwd", &cond_gru_fwd, "fused cond-GRU decoder forward");
+  m.def("cond_gru_fwd", &cond_gru_fwd, "fused cond-GRU decoder forward",
+        py::arg("yg"), py::arg("yc"), py::arg("mask"), py::arg("init_state"),
+        py::arg("ctx_bf"), py::arg("ctx_mask"), py::arg("pctx"),
+        py::arg("Upk2"), py::arg("W1pk"), py::arg("WattPk"), py::arg("b1"),
+        py::arg("bx1"), py::arg("Uatt"), py::arg("catt"), py::arg("Dwei"),
+        py::arg("Wcon"), py::arg("Ucon"), py::arg("accC0"), py::arg("accA0"),
+        py::arg("row_src") = py::none());
   m.def("cond_gru_bwd", &cond_gru_bwd, "fused cond-GRU decoder backward");
 }

@@ -149,16 +149,23 @@ __device__ __forceinline__ void attn_stage_vectors(
 // with the UNNORMALISED p = exp(e - m_c) * mask. cond_attn_combine_gate
 // rescales by exp(m_c - M) / L. pstate arrives as [KS][32][A] split-K
 // partials.
+// With a row_src table (decode against a context kept once per sentence)
+// row b reads source column row_src[b] of the S-column pctx / ctx_mask /
+// ctx_bf; everything else stays per row. An entry outside [0, S) is never
+// dereferenced: the row is treated as fully masked (p = 0, zero partial
+// context), which the combine pass's L == 0 guard turns into alpha = 0.
 __global__ __launch_bounds__(ATT_THREADS) void cond_attn_fwd_chunk(
-    const float* __restrict__ pctx,      // [Ts][B][A]
+    const float* __restrict__ pctx,      // [Ts][S][A]
     const float* __restrict__ ps_part,   // [KS][32][A] pstate partials
     int PS_KS,
     const float* __restrict__ accA,      // [B][Ts] (pre-update)
     const float* __restrict__ Dwei,      // [A]
     const float* __restrict__ Uatt,      // [A]
     const float* __restrict__ catt_p,    // [1]
-    const float* __restrict__ ctx_mask,  // [Ts][B] or null
-    const bf16_t* __restrict__ ctx_bf,   // [Ts][B][C]
+    const float* __restrict__ ctx_mask,  // [Ts][S] or null
+    const bf16_t* __restrict__ ctx_bf,   // [Ts][S][C]
+    const int* __restrict__ row_src,     // [B] source column; null: identity
+    int S,                               // context columns (B without table)
     float* __restrict__ alphas_t,        // [B][Ts] out: unnormalised p
     float* __restrict__ stats,           // [B][NCH][2] out: (m_c, l_c)
     float* __restrict__ ctx_part,        // [B][NCH][C] out
@@ -170,6 +177,8 @@ __global__ __launch_bounds__(ATT_THREADS) void cond_attn_fwd_chunk(
   const float* sm_dw = sm_att + A;
   const float* sm_ua = sm_att + 2 * A;
   const int b = blockIdx.x;
+  const int src = (row_src != nullptr) ? row_src[b] : b;  // block-uniform
+  const bool src_ok = src >= 0 && src < S;
   const int NCH = gridDim.y;
   const int sbeg = blockIdx.y * CH;
   const int n = min(CH, Ts - sbeg);  // >= 1: NCH = ceil(Ts / CH)
@@ -186,11 +195,12 @@ __global__ __launch_bounds__(ATT_THREADS) void cond_attn_fwd_chunk(
     // the real ones — decode results would then depend on how far the
     // source was padded (the graph-decode length bucketing pads to 64)
     const bool live =
-        (ctx_mask == nullptr) || ctx_mask[(long)s * B + b] != 0.f;
+        src_ok &&
+        ((ctx_mask == nullptr) || ctx_mask[(long)s * S + src] != 0.f);
     float e = 0.f;
     if (live) {  // uniform over the lane group
       const float accAu = accA[(long)b * Ts + s];
-      const float* prow = pctx + ((long)s * B + b) * A;
+      const float* prow = pctx + ((long)s * S + src) * A;
       if (A % 4 == 0) {
         for (int i = gl * 4; i < A; i += lps * 4) {
           const float4 p = *(const float4*)(prow + i);
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(ATT_THREADS) void cond_attn_fwd_chunk(
     float p = 0.f;
     if (e != -INFINITY) {  // live, hence m finite
       p = __expf(e - m);
-      if (ctx_mask != nullptr) p *= ctx_mask[(long)(sbeg + ls) * B + b];
+      if (ctx_mask != nullptr) p *= ctx_mask[(long)(sbeg + ls) * S + src];
     }
     float l = p;
 #pragma unroll
@@ -240,8 +250,12 @@ __global__ __launch_bounds__(ATT_THREADS) void cond_attn_fwd_chunk(
   // partial weighted context: each thread owns 8 consecutive c (one 16 B
   // load per source row), eight rows in flight per thread
   float* part = ctx_part + ((long)b * NCH + blockIdx.y) * C;
-  const long sstride = (long)B * C;
-  const bf16_t* cbase = ctx_bf + ((long)sbeg * B + b) * C;
+  if (!src_ok) {  // no source column to load from: the partial is zero
+    for (int c = threadIdx.x; c < C; c += ATT_THREADS) part[c] = 0.f;
+    return;
+  }
+  const long sstride = (long)S * C;
+  const bf16_t* cbase = ctx_bf + ((long)sbeg * S + src) * C;
   const int C8 = C & ~7;
   for (int c0 = threadIdx.x * 8; c0 < C8; c0 += ATT_THREADS * 8) {
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -876,7 +890,8 @@ std::vector<torch::Tensor> cond_gru_fwd(
     torch::Tensor b1, torch::Tensor bx1, torch::Tensor Uatt,
     torch::Tensor catt, torch::Tensor Dwei, torch::Tensor Wcon,
     torch::Tensor Ucon,
-    c10::optional<torch::Tensor> accC0, c10::optional<torch::Tensor> accA0) {
+    c10::optional<torch::Tensor> accC0, c10::optional<torch::Tensor> accA0,
+    c10::optional<torch::Tensor> row_src) {
   const int T = yg.size(0), B = yg.size(1);
   const int H = yc.size(2);
   const int Ts = ctx_bf.size(0), C = ctx_bf.size(2);
@@ -885,6 +900,25 @@ std::vector<torch::Tensor> cond_gru_fwd(
   check_scan_input(yg, torch::kBFloat16, "cond_gru yg");
   check_scan_input(ctx_bf, torch::kBFloat16, "cond_gru ctx");
   check_scan_input(pctx, torch::kFloat32, "cond_gru pctx");
+  // decode against a context kept once per sentence: row b attends to
+  // column row_src[b] of the S-column ctx / pctx / ctx_mask
+  int S = B;
+  const int* row_src_p = nullptr;
+  if (row_src.has_value()) {
+    check_scan_input(*row_src, torch::kInt32, "cond_gru row_src");
+    S = ctx_bf.size(1);
+    TORCH_CHECK(row_src->dim() == 1 && row_src->size(0) == B,
+                "cond_gru: row_src must have one entry per row (", B, ")");
+    TORCH_CHECK(ctx_bf.dim() == 3 && pctx.dim() == 3 && pctx.size(0) == Ts &&
+                    pctx.size(1) == S && pctx.size(2) == A,
+                "cond_gru: with row_src, pctx must be (Ts, S, A) next to a "
+                "(Ts, S, C) ctx");
+    TORCH_CHECK(!ctx_mask.has_value() ||
+                    (ctx_mask->dim() == 2 && ctx_mask->size(0) == Ts &&
+                     ctx_mask->size(1) == S),
+                "cond_gru: with row_src, ctx_mask must be (Ts, S)");
+    row_src_p = row_src->data_ptr<int>();
+  }
   const int Hpad = Upk2.size(1);
   const int K1 = W1pk.size(1);
   const int ngrpH = cdiv(H, JB);
@@ -974,7 +1008,7 @@ std::vector<torch::Tensor> cond_gru_fwd(
                        ps_part.data_ptr<float>(), PS_KS,
                        accA.data_ptr<float>(), Dwei.data_ptr<float>(),
                        Uatt.data_ptr<float>(), catt.data_ptr<float>(),
-                       cmask_p, (const bf16_t*)ctx_bf.data_ptr(),
+                       cmask_p, (const bf16_t*)ctx_bf.data_ptr(), row_src_p, S,
                        alphas_s.at(t), att_stats.data_ptr<float>(),
                        ctx_part.data_ptr<float>(), B, Ts, A, C, CH, lps);
     // 4) attention pass 2: global softmax statistics, combined context,

@@ -21,7 +21,7 @@ from nats_amd.models.distraction import NatsModel, default_options
 
 
 def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False,
-        paged=False):
+        paged=False, shared=False):
     n_tokens = 0
     t0 = time.perf_counter()
     if batched:
@@ -29,6 +29,8 @@ def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False,
         extra = {"fused_select": True} if fused else {}
         if paged:
             extra["paged_rerank"] = True
+        if shared:
+            extra["shared_ctx"] = True
         sb = max(1, 64 // k)
         for base in range(0, len(xs), sb):
             outs = gen_sample_batched(model, xs[base:base + sb], k=k,
@@ -59,6 +61,10 @@ def main():
     ap.add_argument("--maxlen", type=int, default=30)
     ap.add_argument("--dim", type=int, default=500)
     ap.add_argument("--vocab", type=int, default=4000)
+    ap.add_argument("--only", default="",
+                    help="comma-separated variant names to run (default "
+                         "all); peak memory is per variant only when each "
+                         "runs in a process of its own")
     args = ap.parse_args()
 
     device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -91,16 +97,34 @@ def main():
     # paged rerank histories (ops.RerankHistory), appended last
     variants.append(("beam+distraction+batched" + suffix + "+pagedrerank",
                      graph, 0.5, True, True, True))
-    for name, graph, lam, batched, fused, paged in variants:
+    variants = [v + (False,) for v in variants]
+    # beams attend to the per-sentence context (ops.cond_gru_step_shared),
+    # appended last
+    variants.append(("beam+batched" + suffix + "+sharedctx", graph, 0.0,
+                     True, True, False, True))
+    variants.append(("beam+distraction+batched" + suffix +
+                     "+pagedrerank+sharedctx", graph, 0.5, True, True, True,
+                     True))
+    if args.only:
+        variants = [v for v in variants if v[0] in args.only.split(",")]
+    for name, graph, lam, batched, fused, paged, shared in variants:
         run(model, xs[:2], args.k, args.maxlen, graph, lam, batched, fused,
-            paged)
+            paged, shared)
+        if device == "cuda":
+            torch.cuda.reset_peak_memory_stats()
         sps, ntok = run(model, xs, args.k, args.maxlen, graph, lam, batched,
-                        fused, paged)
-        print(json.dumps({
+                        fused, paged, shared)
+        rec = {
             "metric": "summaries_per_sec", "variant": name, "value": sps,
             "beam": args.k, "n": args.n, "src_len": args.src,
             "dim": args.dim, "vocab": args.vocab, "device": device,
-            "data": "synthetic"}))
+            "data": "synthetic"}
+        if device == "cuda":
+            # meaningful only with --only, one variant per process: the
+            # steppers other variants captured stay cached and allocated
+            rec["max_memory_allocated"] = torch.cuda.max_memory_allocated()
+            rec["memory_allocated"] = torch.cuda.memory_allocated()
+        print(json.dumps(rec))
 
 
 if __name__ == "__main__":

@@ -36,6 +36,10 @@ def main():
     ap.add_argument("--paged-rerank", action="store_true",
                     help="paged distraction-rerank histories: one penalty "
                          "call per decode step for all sentences")
+    ap.add_argument("--shared-ctx", action="store_true",
+                    help="attend beams to the per-sentence bf16 context "
+                         "through a row-to-sentence table (no per-row "
+                         "context copies)")
     args = ap.parse_args()
 
     import uvicorn
@@ -48,7 +52,8 @@ def main():
         kl_factor=args.kl_factor, ctx_factor=args.ctx_factor,
         state_factor=args.state_factor, chr_level=args.chr_level,
         max_batch=args.max_batch, max_wait_ms=args.max_wait_ms,
-        fused_select=args.fused_select, paged_rerank=args.paged_rerank)
+        fused_select=args.fused_select, paged_rerank=args.paged_rerank,
+        shared_ctx=args.shared_ctx)
     app = create_app(service)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 

@@ -24,6 +24,12 @@ With ``shared_ctx=True`` the per-sentence context is never expanded to one
 column per hypothesis row: it is rounded to bf16 once per micro-batch and
 the attention kernel reads it through the row -> sentence table
 (ops.cond_gru_step_shared; profiles/README.md, "Decode v6").
+With ``resident_state=True`` the hypothesis rows stay in the stepper's input
+buffers: the host keeps deciding, uploads one table of next-step rows per
+step, and one ops.beam_reorder launch replaces the per-sentence
+index_selects, uploads and concatenations; the alignments' attention rows
+are logged on the device and fetched once (docs/DESIGN.md, "Resident beam
+rows"; profiles/README.md, "Decode v7").
 
 Numerics note: results are mathematically identical to per-sentence
 gen_sample, but not bitwise — the batched masked-mean init state and
@@ -44,7 +50,7 @@ from .beam import distraction_penalties_gpu
 
 def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
                   any_lambda, kl_factor, ctx_factor, state_factor,
-                  paged_pen=None):
+                  paged_pen=None, gather_alpha=True):
     """Phases 1 and 2a of a decode step through ops.beam_select: one upload
     ([running scores | seg_off | want], the fp32 scores carried as their
     int32 bits), one selection call for every alive sentence, one copy of
@@ -54,7 +60,9 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
     them: pend[j] = (i, sl, tis, wis, costs, sel_dev) per alive sentence,
     alpha_sel the selected attention rows in pend order (host array).
     ``paged_pen``: the (R,) rerank penalties of a RerankHistory, used in
-    place of the per-sentence ones."""
+    place of the per-sentence ones. ``gather_alpha=False`` (resident_state:
+    the alignments come from the device log at the end) skips the attention
+    gather and its copy; alpha_sel is then None."""
     device = probs.device
     V = probs.shape[1]
     lives = [st[i]["live"] for i in alive]
@@ -89,11 +97,15 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
     ranks_dev, costs_dev = ops.beam_select(
         probs.float(), prev_dev, seg_dev, want_dev, penalty=penalty,
         use_unk=use_unk, K=K)
-    # batch row of every selection (padding slots point at row seg[s])
-    rows_dev = ranks_dev.clamp_min(0) // V + seg_dev[:-1, None]
+    # batch row of every selection (padding slots point at row seg[s]):
+    # for the attention gather and the dense rerank histories
+    need_rows = gather_alpha or (any_lambda and paged_pen is None)
+    if need_rows:
+        rows_dev = ranks_dev.clamp_min(0) // V + seg_dev[:-1, None]
     sel_host = torch.cat([ranks_dev.double().flatten(),
                           costs_dev.double().flatten()]).cpu().numpy()
-    alpha_pad = alpha.float()[rows_dev.flatten()].cpu().numpy()
+    if gather_alpha:
+        alpha_pad = alpha.float()[rows_dev.flatten()].cpu().numpy()
 
     pend, alpha_rows = [], []
     for j, i in enumerate(alive):
@@ -102,16 +114,18 @@ def _select_fused(st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
         ranks = sel_host[j * K:j * K + want].astype(numpy.int64)
         costs = sel_host[(Sa + j) * K:(Sa + j) * K + want].astype("float32")
         pend.append((i, sl, ranks // V, ranks % V, costs,
-                     rows_dev[j, :want]))
-        alpha_rows.append(alpha_pad[j * K:j * K + want])
-    return pend, numpy.concatenate(alpha_rows)
+                     rows_dev[j, :want] if need_rows else None))
+        if gather_alpha:
+            alpha_rows.append(alpha_pad[j * K:j * K + want])
+    return pend, numpy.concatenate(alpha_rows) if gather_alpha else None
 
 
 @torch.no_grad()
 def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                        kl_factor=0.0, ctx_factor=0.0, state_factor=0.0,
                        use_graph=True, fused_select=False,
-                       paged_rerank=False, shared_ctx=False):
+                       paged_rerank=False, shared_ctx=False,
+                       resident_state=False):
     """Beam-decode a list of sources jointly.
 
     fused_select: pick every sentence's candidates with one
@@ -129,6 +143,17 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
     the per-sentence context (bf16, rounded once) through the sent_idx
     table, instead of gathering ctx / pctx / mask to one column per row
     and re-rounding them on every step. Same results bit for bit. Opt-in.
+
+    resident_state: the hypothesis rows stay in the stepper's input
+    buffers. The host decides as ever (samples, scores, dead counts, EOS);
+    per step it uploads one (3, L) table [parent row | word | sentence] of
+    the next step's rows and one ops.beam_reorder call moves h2 / acc_ctx /
+    acc_alpha from the step's outputs into its inputs, writes the words and
+    the routing and pads the tail, in place of the per-sentence
+    index_selects, uploads and concatenations. Attention rows are logged
+    on the device per step and fetched once at the end for the alignments.
+    Every value is a copy of what the default path produces: same results
+    bit for bit. Opt-in.
 
     xs: list of (T_i, 1) int64 tensors (same device as model).
     maxlen: an int, or a per-sentence list (serving: each request brings
@@ -205,6 +230,17 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
         stepper = get_batched_stepper(model, ctx_pad.float(), ctx_mask_s,
                                       pctx_pad.float(), S * k,
                                       shared_ctx=shared_ctx)
+    resident = bool(resident_state)
+    if resident and stepper is None:
+        # the same buffers without a graph: one code path below for both
+        from .graph import RowStepper
+        if shared_ctx:
+            stepper = RowStepper(model, ctx_dec, cmask_dec, pctx_pad, S * k,
+                                 shared_ctx=True)
+        else:
+            stepper = RowStepper(model, ctx_pad, ctx_mask_s, pctx_pad, S * k)
+    table_dev = None  # resident: the (3, L) table of the step to run
+    alog = None       # resident: (max(maxlens), S*k, Ts) log of alpha rows
 
     NEG_UNK = math.log(1e-20)
 
@@ -222,39 +258,48 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
         alive = [i for i in range(S) if st[i]["live"] > 0]
         if not alive:
             break
-        sent_rows = sum(([i] * st[i]["live"] for i in alive), [])
-        if paged:
-            # the parents of the ancestor-table advance ride along with
-            # sent_idx: one upload for both
-            up = torch.tensor(
-                sent_rows + sum((st[i]["prows"] for i in alive), []),
-                device=device)
-            sent_idx, parent_dev = up[:len(sent_rows)], up[len(sent_rows):]
-        elif stepper is not None or not shared_ctx:
-            sent_idx = torch.tensor(sent_rows, device=device)
-        y = torch.cat([dstate[i]["w"] for i in alive])
-        state = torch.cat([dstate[i]["state"] for i in alive])
-        acc_c = torch.cat([dstate[i]["acc_c"] for i in alive])
-        acc_a = torch.cat([dstate[i]["acc_a"] for i in alive])
-        if stepper is None and not shared_ctx:
-            ctx_b = ctx_pad[:, sent_idx]
-            cmask_b = ctx_mask_s[:, sent_idx]
-            pctx_b = pctx_pad[:, sent_idx]
-
-        if stepper is not None:
-            rows = y.shape[0]
-            outs = stepper.step(sent_idx, y, state.float(), acc_c.float(),
-                                acc_a.float())
+        if resident and ii > 0:
+            # the rows are in the stepper's buffers already (beam_reorder
+            # at the end of the previous step)
+            rows = table_dev.shape[1]
+            parent_dev = table_dev[0]
             probs, h2, alpha, ctx_t, acc_c, acc_a = [
-                o[:rows] for o in outs]
-        elif shared_ctx:
-            probs, _, h2, alpha, ctx_t, acc_c, acc_a = model.f_next(
-                y, ctx_dec, cmask_dec, pctx_pad, state, acc_c, acc_a,
-                sample_draw=False, row_src=sent_rows)  # validated, 1 upload
+                o[:rows] for o in stepper.replay(rows)]
         else:
-            probs, _, h2, alpha, ctx_t, acc_c, acc_a = model.f_next(
-                y, ctx_b, cmask_b, pctx_b, state, acc_c, acc_a,
-                sample_draw=False)
+            sent_rows = sum(([i] * st[i]["live"] for i in alive), [])
+            if paged:
+                # the parents of the ancestor-table advance ride along with
+                # sent_idx: one upload for both
+                up = torch.tensor(
+                    sent_rows + sum((st[i]["prows"] for i in alive), []),
+                    device=device)
+                sent_idx, parent_dev = up[:len(sent_rows)], up[len(sent_rows):]
+            elif stepper is not None or not shared_ctx:
+                sent_idx = torch.tensor(sent_rows, device=device)
+            y = torch.cat([dstate[i]["w"] for i in alive])
+            state = torch.cat([dstate[i]["state"] for i in alive])
+            acc_c = torch.cat([dstate[i]["acc_c"] for i in alive])
+            acc_a = torch.cat([dstate[i]["acc_a"] for i in alive])
+            if stepper is None and not shared_ctx:
+                ctx_b = ctx_pad[:, sent_idx]
+                cmask_b = ctx_mask_s[:, sent_idx]
+                pctx_b = pctx_pad[:, sent_idx]
+
+            if stepper is not None:
+                rows = y.shape[0]
+                outs = stepper.step(sent_idx, y, state.float(), acc_c.float(),
+                                    acc_a.float())
+                probs, h2, alpha, ctx_t, acc_c, acc_a = [
+                    o[:rows] for o in outs]
+            elif shared_ctx:
+                probs, _, h2, alpha, ctx_t, acc_c, acc_a = model.f_next(
+                    y, ctx_dec, cmask_dec, pctx_pad, state, acc_c, acc_a,
+                    sample_draw=False,
+                    row_src=sent_rows)  # validated, 1 upload
+            else:
+                probs, _, h2, alpha, ctx_t, acc_c, acc_a = model.f_next(
+                    y, ctx_b, cmask_b, pctx_b, state, acc_c, acc_a,
+                    sample_draw=False)
         V = probs.shape[1]
 
         paged_pen = None
@@ -268,10 +313,25 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 ctx_t.float().contiguous(), h2.float().contiguous(),
                 (kl_factor, ctx_factor, state_factor))
 
+        if resident:
+            # every row's attention, before selection: the alignments are
+            # gathered from this log once, after the last step
+            if paged:
+                alog = history.hist_a  # the rerank slab already is that log
+            else:
+                if alog is None:
+                    alog = torch.empty(max(maxlens), S * k, alpha.shape[1],
+                                       device=device)
+                alog[ii, :rows] = alpha
+        # the selected rows as a device tensor: only the dense rerank
+        # histories still need them when the rows stay resident
+        need_sel = not resident or (any_lambda and not paged)
+
         if fused_select:
             pend, alpha_sel = _select_fused(
                 st, dstate, alive, k, ii, probs, alpha, ctx_t, h2, use_unk,
-                any_lambda, kl_factor, ctx_factor, state_factor, paged_pen)
+                any_lambda, kl_factor, ctx_factor, state_factor, paged_pen,
+                gather_alpha=not resident)
         else:
             # -- phase 1: per-sentence top-k ON DEVICE, one host transfer --
             logp = probs.float().log()
@@ -318,23 +378,32 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                 off += 2 * want
                 tis = ranks // V
                 wis = ranks % V
-                sel_dev = torch.as_tensor(tis, device=device) + sl.start
-                alpha_gather.append(alpha.float()[sel_dev])
+                sel_dev = None
+                if need_sel:
+                    sel_dev = torch.as_tensor(tis, device=device) + sl.start
+                if not resident:
+                    alpha_gather.append(alpha.float()[sel_dev])
                 pend.append((i, sl, tis, wis, costs, sel_dev))
-            alpha_sel = torch.cat(alpha_gather).cpu().numpy()
+            alpha_sel = None
+            if not resident:
+                alpha_sel = torch.cat(alpha_gather).cpu().numpy()
 
         arow = 0
+        tab_p, tab_w, tab_s = [], [], []  # resident: the next step's rows
         for i, sl, tis, wis, costs, sel_dev in pend:
             want = len(tis)
-            a_np = alpha_sel[arow:arow + want]
+            if not resident:
+                a_np = alpha_sel[arow:arow + want]
             arow += want
 
             new_samples, new_scores, new_alphas, new_words = [], [], [], []
             for r, (ti, wi) in enumerate(zip(tis, wis)):
                 new_samples.append(st[i]["samples"][ti] + [int(wi)])
                 new_scores.append(float(costs[r]))
-                new_alphas.append(st[i]["alphas"][ti] +
-                                  [a_np[r, :lens[i]].copy()])
+                # resident: (step, batch row) into the device log
+                new_alphas.append(st[i]["alphas"][ti] + [
+                    (ii, sl.start + int(ti)) if resident
+                    else a_np[r, :lens[i]].copy()])
                 new_words.append(int(wi))
 
             # device histories for the rerank (pre-filter selection order)
@@ -369,7 +438,18 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
             st[i]["live"] = len(samples)
             if st[i]["dead"] >= k:
                 st[i]["live"] = 0
-            if st[i]["live"] > 0:
+            if st[i]["live"] > 0 and resident:
+                # a sentence at its cap after this step leaves the table
+                if ii + 1 < maxlens[i]:
+                    tab_p += [sl.start + int(tis[j]) for j in keep]
+                    tab_w += words_l
+                    tab_s += [i] * len(keep)
+                if any_lambda and not paged:
+                    kt = torch.tensor(keep, dtype=torch.int64, device=device)
+                    dstate[i]["ha"] = ha[:, kt]
+                    dstate[i]["hc"] = hc[:, kt]
+                    dstate[i]["hs"] = hs[:, kt]
+            elif st[i]["live"] > 0:
                 kt = torch.tensor(keep, dtype=torch.int64, device=device)
                 sel_keep = sel_dev[kt]
                 dstate[i]["w"] = torch.tensor(words_l, dtype=torch.int64,
@@ -384,6 +464,16 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
                     dstate[i]["hc"] = hc[:, kt]
                     dstate[i]["hs"] = hs[:, kt]
 
+        if tab_p:
+            # one upload, one launch: the kept rows move from this step's
+            # outputs into the next step's inputs, with their words, their
+            # routing and the padding tail
+            dsts, y_buf, route_buf = stepper.resident_buffers()
+            table_dev = ops.beam_reorder(
+                [tab_p, tab_w, tab_s],
+                tuple(t.float().contiguous() for t in (h2, acc_c, acc_a)),
+                dsts, y_buf, route_buf)
+
     results = []
     for i in range(S):
         out_s = list(st[i]["out_samples"])
@@ -394,4 +484,25 @@ def gen_sample_batched(model, xs, k=1, maxlen=30, use_unk=False,
             out_c.append(float(st[i]["scores"][idx2]))
             out_a.append(st[i]["alphas"][idx2])
         results.append((out_s, out_c, out_a))
+    if resident:
+        _fetch_alignments(results, alog, lens)
     return results
+
+
+def _fetch_alignments(results, alog, lens):
+    """resident_state: replace the (step, batch row) references of every
+    hypothesis by the attention rows they name, read from the device log
+    ``alog`` (steps, rows, Ts) with one gather and one copy to the host,
+    trimmed to the sentence's own length."""
+    refs = [ref for _, _, out_a in results for hyp in out_a for ref in hyp]
+    if not refs:
+        return
+    width = alog.shape[1]
+    idx = torch.tensor([s * width + r for s, r in refs]).to(alog.device)
+    got = alog.reshape(-1, alog.shape[2])[idx].cpu().numpy()
+    pos = 0
+    for i, (_, _, out_a) in enumerate(results):
+        for h, hyp in enumerate(out_a):
+            out_a[h] = [got[pos + t, :lens[i]].copy()
+                        for t in range(len(hyp))]
+            pos += len(hyp)

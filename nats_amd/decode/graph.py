@@ -110,17 +110,30 @@ class _GraphStepper:
         rows, one value per buffer of ``self.inputs``; returns (probs,
         state, alpha, ctx_t, acc_ctx, acc_alpha), each ``rows`` rows —
         callers slice [:live]."""
-        live = values[0].shape[0]
-        for buf, v in zip(self.inputs, values):
-            buf[:live] = v
-        if live < self.rows:
-            for buf, v in zip(self.inputs, values):
-                buf[live:] = v[0]
+        _fill_rows(self.inputs, values, self.rows)
+        return self.replay()
+
+    def replay(self, live=None):
+        """Replay the captured graph on the input buffers as they stand
+        (``step`` or ops.beam_reorder wrote them); captures on first use.
+        Same returns as ``step``. ``live`` is not needed here: all ``rows``
+        rows run (RowStepper, the graph-less twin, runs the live ones)."""
         if self.graph is None:
             self.capture()
         self.graph.replay()
         probs, _, h2, alpha, ctx_t, accC, accA = self.outs
         return probs, h2, alpha, ctx_t, accC, accA
+
+
+def _fill_rows(inputs, values, rows):
+    """Write ``values`` (live rows each) into the static buffers and pad the
+    tail with copies of row 0."""
+    live = values[0].shape[0]
+    for buf, v in zip(inputs, values):
+        buf[:live] = v
+    if live < rows:
+        for buf, v in zip(inputs, values):
+            buf[live:] = v[0]
 
 
 class GraphDecodeStepper(_GraphStepper):
@@ -199,6 +212,13 @@ class BatchedGraphStepper(_GraphStepper):
         self.ctx_mask.copy_(ctx_mask)
         self.pctx_pad.copy_(pctx_pad)
 
+    def resident_buffers(self):
+        """What ops.beam_reorder writes between two ``replay`` calls:
+        ((state_in, accC_in, accA_in), y_in, route buffer), the route
+        buffer being ``sent_idx`` (int64) or, in shared mode, ``row_src``
+        (int32)."""
+        return self.inputs[2:], self.y_in, self.inputs[0]
+
     def _run(self):
         if self.shared_ctx:
             return self.model.f_next(self.y_in, self.ctx_pad, self.ctx_mask,
@@ -212,3 +232,60 @@ class BatchedGraphStepper(_GraphStepper):
         return self.model.f_next(self.y_in, ctx_b, cmask_b, pctx_b,
                                  self.state_in, self.accC_in, self.accA_in,
                                  sample_draw=False)
+
+
+class RowStepper:
+    """BatchedGraphStepper without the graph (CPU, or use_graph=False), for
+    the resident-state decode: a plain holder of the same per-row buffers,
+    with the same ``step`` / ``replay`` / ``resident_buffers``. f_next runs
+    on the ``[:live]`` views, uncaptured, against the caller's context
+    (not copied: the holder lives for one decode). ``shared_ctx``: ctx /
+    ctx_mask / pctx are NatsModel.decode_context's per-source operands and
+    the route buffer is the int32 row -> source table."""
+
+    def __init__(self, model, ctx, ctx_mask, pctx, R, shared_ctx=False):
+        Ts, _, C = ctx.shape
+        device = ctx.device
+        self.model = model
+        self.rows = R
+        self.shared_ctx = shared_ctx
+        self.ctx, self.ctx_mask, self.pctx = ctx, ctx_mask, pctx
+        self.route = torch.zeros(
+            R, dtype=torch.int32 if shared_ctx else torch.int64,
+            device=device)
+        self.y_in = torch.zeros(R, dtype=torch.int64, device=device)
+        self.state_in = torch.zeros(R, model.options["dim"], device=device)
+        self.accC_in = torch.zeros(R, C, device=device)
+        self.accA_in = torch.zeros(R, Ts, device=device)
+        self.inputs = (self.route, self.y_in, self.state_in, self.accC_in,
+                       self.accA_in)
+
+    def resident_buffers(self):
+        return self.inputs[2:], self.y_in, self.route
+
+    def step(self, *values):
+        """Fill the buffers from (sent_idx, y, state, acc_ctx, acc_alpha)
+        and run the step; returns ``replay``'s six outputs."""
+        _fill_rows(self.inputs, values, self.rows)
+        return self.replay(values[0].shape[0])
+
+    def replay(self, live):
+        """f_next on the first ``live`` rows of the buffers as they stand:
+        (probs, state, alpha, ctx_t, acc_ctx, acc_alpha), ``live`` rows
+        each, none of them a view of a buffer."""
+        route = self.route[:live]
+        # the step kernels update fp32 contiguous accumulators in place:
+        # they get copies, so that ops.beam_reorder can read the outputs
+        # while it writes the buffers
+        args = (self.state_in[:live], self.accC_in[:live].clone(),
+                self.accA_in[:live].clone())
+        if self.shared_ctx:
+            outs = self.model.f_next(
+                self.y_in[:live], self.ctx, self.ctx_mask, self.pctx, *args,
+                sample_draw=False, row_src=route)
+        else:
+            outs = self.model.f_next(
+                self.y_in[:live], self.ctx[:, route], self.ctx_mask[:, route],
+                self.pctx[:, route], *args, sample_draw=False)
+        probs, _, h2, alpha, ctx_t, accC, accA = outs
+        return probs, h2, alpha, ctx_t, accC, accA

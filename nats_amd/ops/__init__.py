@@ -442,6 +442,147 @@ def beam_select(probs, prev_cost, seg_off, want, penalty=None, use_unk=True,
                              use_unk, K)
 
 
+BEAM_REORDER_MAX_BUFFERS = 4  # pointer slots of ReorderArgs (beam_reorder.hip)
+
+
+def _reorder_table(table, L_max, n_prev, device):
+    """The (3, L) int64 [parent | word | sentence] table of beam_reorder on
+    ``device``. A nested list or a CPU integer tensor is validated and
+    uploaded in one copy; an int64 device tensor is taken on trust (reading
+    it would sync)."""
+    op = "beam_reorder"
+    if torch.is_tensor(table):
+        if table.dtype not in (torch.int32, torch.int64) or \
+                table.dim() != 2 or table.shape[0] != 3:
+            raise TypeError("%s: table must be a (3, L) integer tensor, got "
+                            "%s %s" % (op, table.dtype, tuple(table.shape)))
+        if table.is_cuda:
+            if table.dtype != torch.int64:
+                raise TypeError("%s: a device table must be int64, got %s"
+                                % (op, table.dtype))
+            if not 1 <= table.shape[1] <= L_max:
+                raise ValueError("%s: L=%d rows outside [1, Rmax=%d]"
+                                 % (op, table.shape[1], L_max))
+            return table.contiguous()
+        rows = table.tolist()
+    else:
+        rows = [list(r) for r in table]
+        if len(rows) != 3 or len({len(r) for r in rows}) != 1:
+            raise ValueError("%s: table must be three rows of one length "
+                             "[parent | word | sentence]" % op)
+        if any(isinstance(v, bool) or not isinstance(v, int)
+               for r in rows for v in r):
+            raise TypeError("%s: table entries must be integers" % op)
+    L = len(rows[0])
+    if not 1 <= L <= L_max:
+        raise ValueError("%s: L=%d rows outside [1, Rmax=%d]"
+                         % (op, L, L_max))
+    for r in range(L):
+        if not 0 <= rows[0][r] < n_prev:
+            raise ValueError("%s: parent[%d]=%d outside the previous step's "
+                             "%d rows" % (op, r, rows[0][r], n_prev))
+        if rows[1][r] < -1:
+            raise ValueError("%s: word[%d]=%d below -1"
+                             % (op, r, rows[1][r]))
+        if rows[2][r] < 0:
+            raise ValueError("%s: sentence[%d]=%d is negative"
+                             % (op, r, rows[2][r]))
+    return torch.tensor(rows, dtype=torch.int64).to(device,
+                                                    non_blocking=True)
+
+
+def _byte_range(t):
+    return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+
+
+def beam_reorder(table, src, dst, y_out, route_out, n_prev=None):
+    """Move the beam rows the host selected from a decode step's outputs
+    into the next step's input buffers, in one call (one kernel launch on
+    the GPU): for r < L ``dst_j[r] = src_j[parent[r]]``, ``y_out[r] =
+    word[r]``, ``route_out[r] = sentence[r]``; every row ``L <= r < Rmax``
+    becomes a copy of the new row 0 (the padding rule of the decode
+    steppers).
+
+    table (3, L) = [parent | word | sentence], 1 <= L <= Rmax: a nested list
+    or CPU integer tensor (validated: parent in [0, n_prev), word >= -1,
+    sentence >= 0; one upload) or an int64 device tensor (taken on trust; a
+    parent outside [0, n_prev) is never dereferenced: that row's dst_j
+    become NaN, its y_out and route_out 0). src: up to four (>= n_prev, D_j)
+    fp32 contiguous tensors, n_prev defaults to ``src[0].shape[0]``; dst:
+    the matching (Rmax, D_j) fp32 contiguous buffers, none overlapping a
+    src; y_out (Rmax,) int64; route_out (Rmax,) int64 or int32.
+
+    Returns the table as the (3, L) int64 tensor on the buffers' device:
+    its row 0 is the ``parent`` of RerankHistory.step.
+    """
+    op = "beam_reorder"
+    src, dst = tuple(src), tuple(dst)
+    if not 1 <= len(src) <= BEAM_REORDER_MAX_BUFFERS or len(dst) != len(src):
+        raise ValueError("%s: need 1 to %d src buffers and as many dst "
+                         "buffers, got %d and %d" % (
+                             op, BEAM_REORDER_MAX_BUFFERS, len(src),
+                             len(dst)))
+    for name, t in (("y_out", y_out), ("route_out", route_out)):
+        if (not torch.is_tensor(t) or t.dim() != 1 or t.dtype not in
+                ((torch.int64,) if name == "y_out"
+                 else (torch.int64, torch.int32))):
+            raise TypeError("%s: %s must be a 1-d int64%s tensor, got %s %s"
+                            % (op, name,
+                               "" if name == "y_out" else " or int32",
+                               getattr(t, "dtype", type(t)),
+                               tuple(getattr(t, "shape", ()))))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (op, name))
+    Rmax, device = y_out.shape[0], y_out.device
+    if route_out.shape[0] != Rmax:
+        raise ValueError("%s: route_out has %d entries, y_out %d"
+                         % (op, route_out.shape[0], Rmax))
+    for j, (s, d) in enumerate(zip(src, dst)):
+        for name, t in (("src", s), ("dst", d)):
+            if (not torch.is_tensor(t) or t.dtype != torch.float32
+                    or t.dim() != 2):
+                raise TypeError("%s: %s[%d] must be a 2-d float32 tensor, "
+                                "got %s %s" % (
+                                    op, name, j, getattr(t, "dtype", type(t)),
+                                    tuple(getattr(t, "shape", ()))))
+            if not t.is_contiguous():
+                raise ValueError("%s: %s[%d] must be contiguous"
+                                 % (op, name, j))
+            if t.device != device:
+                raise ValueError("%s: %s[%d] is on %s, y_out on %s"
+                                 % (op, name, j, t.device, device))
+        if s.shape[1] != d.shape[1] or s.shape[1] < 1:
+            raise ValueError("%s: src[%d] %s and dst[%d] %s disagree in row "
+                             "width" % (op, j, tuple(s.shape), j,
+                                        tuple(d.shape)))
+        if d.shape[0] != Rmax:
+            raise ValueError("%s: dst[%d] has %d rows, y_out %d"
+                             % (op, j, d.shape[0], Rmax))
+    n_prev = src[0].shape[0] if n_prev is None else int(n_prev)
+    if n_prev < 1 or any(s.shape[0] < n_prev for s in src):
+        raise ValueError("%s: n_prev=%d does not fit src buffers of %s rows"
+                         % (op, n_prev, [s.shape[0] for s in src]))
+    for j, s in enumerate(src):
+        s0, s1 = _byte_range(s)
+        for i, d in enumerate(dst):
+            d0, d1 = _byte_range(d)
+            if s0 < d1 and d0 < s1:
+                raise ValueError("%s: src[%d] and dst[%d] overlap: rows "
+                                 "would be read after they are written"
+                                 % (op, j, i))
+    if route_out.device != device or (torch.is_tensor(table) and table.is_cuda
+                                      and table.device != device):
+        raise ValueError("%s: table, y_out and route_out must share the "
+                         "buffers' device" % op)
+    table = _reorder_table(table, Rmax, n_prev, device)
+    if _use_hip(y_out, *dst):
+        _hip_ext().beam_reorder(table, list(src), list(dst), y_out,
+                                route_out, n_prev)
+    else:
+        eager.beam_reorder(table, src, dst, y_out, route_out, n_prev)
+    return table
+
+
 def softmax_xent(logits, targets):
     """Per-position NLL of a softmax over the vocabulary.
 

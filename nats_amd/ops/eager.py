@@ -283,3 +283,26 @@ def rerank_penalties_paged(hist_a, hist_c, hist_s, anc, n, cur_a, cur_c,
         rerank_gather(hist_a, anc, n, R), rerank_gather(hist_c, anc, n, R),
         rerank_gather(hist_s, anc, n, R), cur_a, cur_c, cur_s,
         kl_factor, ctx_factor, state_factor)
+
+
+def beam_reorder(table, src, dst, y_out, route_out, n_prev):
+    """Beam-row reshuffle of a batched decode step, as index_selects.
+    table (3, L) int64 on the buffers' device = [parent | word | sentence];
+    for r < L: dst_j[r] = src_j[parent[r]], y_out[r] = word[r],
+    route_out[r] = sentence[r]; rows L <= r < Rmax repeat the new row 0. A
+    parent outside [0, n_prev) is not dereferenced: NaN rows, y and route 0
+    (the kernel's poison convention)."""
+    L, Rmax = table.shape[1], y_out.shape[0]
+    cols = torch.arange(Rmax, device=table.device)
+    tab = table.index_select(1, torch.where(cols < L, cols,
+                                            torch.zeros_like(cols)))
+    parent = tab[0]
+    ok = (parent >= 0) & (parent < n_prev)
+    safe = torch.where(ok, parent, torch.zeros_like(parent))
+    for s, d in zip(src, dst):
+        rows = s.index_select(0, safe)
+        d.copy_(torch.where(ok[:, None], rows,
+                            torch.full_like(rows, float("nan"))))
+    zero = torch.zeros_like(parent)
+    y_out.copy_(torch.where(ok, tab[1], zero))
+    route_out.copy_(torch.where(ok, tab[2], zero))

@@ -49,6 +49,9 @@ std::vector<torch::Tensor> beam_select(torch::Tensor probs,
                                        torch::Tensor want,
                                        c10::optional<torch::Tensor> penalty,
                                        long K, bool use_unk, double neg_unk);
+void beam_reorder(torch::Tensor table, std::vector<torch::Tensor> src,
+                  std::vector<torch::Tensor> dst, torch::Tensor y_out,
+                  torch::Tensor route_out, long n_prev);
 void fused_adadelta_step(torch::Tensor ptrs, torch::Tensor sizes,
                          torch::Tensor chunk_tensor, torch::Tensor chunk_off,
                          torch::Tensor g2, double clip_c, double rho,
@@ -141,6 +144,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "table (partial pass + combine pass)");
   m.def("beam_select", &beam_select,
         "segmented beam candidate selection (tile pass + merge pass)");
+  m.def("beam_reorder", &beam_reorder,
+        "beam-row gather into the decode step's input buffers (+ words, "
+        "routing, padding tail)");
   m.def("fused_adadelta_step", &fused_adadelta_step,
         "fused multi-tensor global-norm clip + adadelta");
   m.def("cond_gru_fwd", &cond_gru_fwd, "fused cond-GRU decoder forward",

@@ -21,6 +21,7 @@ SOURCES = [
     os.path.join(HERE, "optim.hip"),
     os.path.join(HERE, "rerank.hip"),
     os.path.join(HERE, "beam_select.hip"),
+    os.path.join(HERE, "beam_reorder.hip"),
     os.path.join(HERE, "embed.hip"),
     os.path.join(HERE, "pack.hip"),
     os.path.join(HERE, "io_fusion.hip"),

@@ -41,15 +41,17 @@ class SummarizerService:
     candidates with one ops.beam_select call, ``paged_rerank`` keeps the
     distraction-rerank histories in one ops.RerankHistory, ``shared_ctx``
     attends the beams to the per-sentence context through a row -> sentence
-    table instead of expanding it per row (all gen_sample_batched options,
-    off by default).
+    table instead of expanding it per row, ``resident_state`` keeps the beam
+    rows in the stepper's buffers between steps (all gen_sample_batched
+    options, off by default).
     """
 
     def __init__(self, model_path, dictionary, device=None, k=10, maxlen=100,
                  normalize=True, kl_factor=0.0, ctx_factor=0.0,
                  state_factor=0.0, chr_level=False, max_batch=None,
                  max_wait_ms=5.0, fused_select=False,
-                 paged_rerank=False, shared_ctx=False):
+                 paged_rerank=False, shared_ctx=False,
+                 resident_state=False):
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = device
@@ -63,6 +65,7 @@ class SummarizerService:
         self.fused_select = bool(fused_select)
         self.paged_rerank = bool(paged_rerank)
         self.shared_ctx = bool(shared_ctx)
+        self.resident_state = bool(resident_state)
         self.max_batch = int(max_batch or max(1, 64 // self.k))
         self.max_wait_s = float(max_wait_ms) / 1000.0
         self.model_path = str(model_path)
@@ -195,7 +198,8 @@ class SummarizerService:
                 state_factor=self.state_factor,
                 fused_select=self.fused_select,
                 paged_rerank=self.paged_rerank,
-                shared_ctx=self.shared_ctx)
+                shared_ctx=self.shared_ctx,
+                resident_state=self.resident_state)
         results = []
         for src_words, (sample, score, alphas) in zip(srcs, outs):
             score = numpy.array(score, dtype=numpy.float64)

@@ -21,7 +21,7 @@ from nats_amd.models.distraction import NatsModel, default_options
 
 
 def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False,
-        paged=False, shared=False):
+        paged=False, shared=False, resident=False):
     n_tokens = 0
     t0 = time.perf_counter()
     if batched:
@@ -31,6 +31,8 @@ def run(model, xs, k, maxlen, use_graph, lam, batched=False, fused=False,
             extra["paged_rerank"] = True
         if shared:
             extra["shared_ctx"] = True
+        if resident:
+            extra["resident_state"] = True
         sb = max(1, 64 // k)
         for base in range(0, len(xs), sb):
             outs = gen_sample_batched(model, xs[base:base + sb], k=k,
@@ -105,15 +107,23 @@ def main():
     variants.append(("beam+distraction+batched" + suffix +
                      "+pagedrerank+sharedctx", graph, 0.5, True, True, True,
                      True))
+    variants = [v + (False,) for v in variants]
+    # beam rows resident in the stepper's buffers (ops.beam_reorder),
+    # appended last
+    variants.append(("beam+batched" + suffix + "+sharedctx+resident", graph,
+                     0.0, True, True, False, True, True))
+    variants.append(("beam+distraction+batched" + suffix +
+                     "+pagedrerank+sharedctx+resident", graph, 0.5, True, True,
+                     True, True, True))
     if args.only:
         variants = [v for v in variants if v[0] in args.only.split(",")]
-    for name, graph, lam, batched, fused, paged, shared in variants:
+    for name, graph, lam, batched, fused, paged, shared, resident in variants:
         run(model, xs[:2], args.k, args.maxlen, graph, lam, batched, fused,
-            paged, shared)
+            paged, shared, resident)
         if device == "cuda":
             torch.cuda.reset_peak_memory_stats()
         sps, ntok = run(model, xs, args.k, args.maxlen, graph, lam, batched,
-                        fused, paged, shared)
+                        fused, paged, shared, resident)
         rec = {
             "metric": "summaries_per_sec", "variant": name, "value": sps,
             "beam": args.k, "n": args.n, "src_len": args.src,

@@ -40,6 +40,10 @@ def main():
                     help="attend beams to the per-sentence bf16 context "
                          "through a row-to-sentence table (no per-row "
                          "context copies)")
+    ap.add_argument("--resident-state", action="store_true",
+                    help="keep the beam rows in the decode step's device "
+                         "buffers: one table upload and one reorder launch "
+                         "per step")
     args = ap.parse_args()
 
     import uvicorn
@@ -53,7 +57,7 @@ def main():
         state_factor=args.state_factor, chr_level=args.chr_level,
         max_batch=args.max_batch, max_wait_ms=args.max_wait_ms,
         fused_select=args.fused_select, paged_rerank=args.paged_rerank,
-        shared_ctx=args.shared_ctx)
+        shared_ctx=args.shared_ctx, resident_state=args.resident_state)
     app = create_app(service)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 
